@@ -15,6 +15,11 @@ seal digests). The ranks come from torch.distributed.run, or — when `--gpus N`
 without a launcher — from risc0_amd.segments.launch_local, which starts N rank processes
 (rank r on device r) before anything touches a GPU, as r0vm spawns one worker per GPU.
 
+A plain run sets up, warms up, times --steps segments and prints the line; --full adds the side
+legs (resident_trace, prove_only, per_op_abi, end_to_end, with_accumulation), the one-segment
+latency, the roofline and the CPU baseline with its seal parity. --dump-outputs DIR writes the
+last timed step's seal and mix values as .npy files.
+
 Prints ONE JSON line (rank 0). Extra diagnostics go to stderr.
 """
 import argparse
@@ -43,6 +48,15 @@ def parse():
     ap.add_argument("--po2", type=int, default=20)
     ap.add_argument("--circuit", default="rv32im")
     ap.add_argument("--hashfn", default="poseidon2")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run the side legs and checks (resident_trace, prove_only, "
+                         "per_op_abi, end_to_end, with_accumulation, the one-segment latency, the roofline and the CPU "
+                         "baseline with its seal parity); the options below that size or skip a leg apply only here. "
+                         "Without it the run sets up, warms up, times --steps segments and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned to its caller (the seal and the transcript's mix "
+                         "values, u32 words held exactly in float64) as DIR/seal.npy and DIR/mix.npy (ranks above 0: "
+                         "DIR/seal_rank<r>.npy, DIR/mix_rank<r>.npy); the inputs are seeded, so equal arguments give equal files")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-prove-only", action="store_true",
                     help="trace mode: skip the prove_only leg (profiling runs count only trace proofs)")
@@ -84,7 +98,20 @@ def parse():
     ap.add_argument("--inflight", type=int, default=None,
                     help="segments in flight per GPU (host threads, each with its own HIP stream); "
                          "default 6 up to po2=18, 3 up to po2=20, 2 up to po2=22, 1 above (one po2=24 segment needs ~150 GB)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if not args.full:
+        # a plain run measures the headline alone: every side leg off
+        args.no_cpu_baseline = args.no_prove_only = True
+        args.resident_steps = args.e2e_steps = args.accum_steps = args.per_op_steps = 0
+    return args
+
+
+def dump_outputs(dirname, rank, seal, mix):
+    """--dump-outputs: the last timed step's seal and mix values (u32 words, exact in float64)."""
+    os.makedirs(dirname, exist_ok=True)
+    tag = "" if rank == 0 else f"_rank{rank}"
+    for name, a in (("seal", seal), ("mix", mix)):
+        np.save(os.path.join(dirname, name + tag + ".npy"), np.ascontiguousarray(a).reshape(-1).astype(np.float64))
 
 
 def synthetic_witness(rng, circuit, po2):
@@ -135,9 +162,19 @@ def main():
     hal = r.HipHal(args.hashfn, device=device)
     version = 2 if args.circuit == "rv32im" else None
 
-    # inputs resident in HBM before the timed region: one witness set per rank
+    trace_mode = args.circuit == "rv32im" and not args.witness
+    # recursion: a whole proof from the program and its preflight (RecursionProverImpl::prove,
+    # circuit/recursion/src/prove/mod.rs:160-230: witness generation, ZK noise, accumulation,
+    # prove), the lift/join shape with random programs (the lift/join .zkr files are not in the
+    # reference checkout)
+    program_mode = args.circuit == "recursion" and not args.witness
+
+    # inputs resident in HBM before the timed region: one witness set per rank (the --witness
+    # headline and the side legs of --full prove it; a plain trace or program run needs none)
     rng = np.random.default_rng(0x5249534330 + rank)
-    if args.po2 <= 22:
+    if not args.full and (trace_mode or program_mode):
+        glob = dc = dd = da = dg = host_witness = None
+    elif args.po2 <= 22:
         code, data, accum, glob = synthetic_witness(rng, circ, args.po2)
         dc, dd, da, dg = (hal.copy_from_elem(k, v) for k, v in
                           (("code", code), ("data", data), ("accum", accum), ("global", glob)))
@@ -165,17 +202,11 @@ def main():
     k = max(1, min(inflight, len(segs) or 1))
     # per-thread globals buffer: prove_segment zeroizes it in place; the witness
     # groups are only read and are shared
-    globs = [dg] + [hal.copy_from_elem("global", glob) for _ in range(k - 1)]
-    trace_mode = args.circuit == "rv32im" and not args.witness
+    globs = [dg] + [hal.copy_from_elem("global", glob) for _ in range(k - 1)] if dg is not None else []
     if trace_mode and args.guest == "loop_s" and not args.no_session and args.session is None and args.po2 <= 22:
         # the default workload: N x steps consecutive segments of one loop.s run, segment i on
         # rank i mod N (configs[1] per segment, configs[3] across the ranks)
         args.session = world * args.steps
-    # recursion: a whole proof from the program and its preflight (RecursionProverImpl::prove,
-    # circuit/recursion/src/prove/mod.rs:160-230: witness generation, ZK noise, accumulation,
-    # prove), the lift/join shape with random programs (the lift/join .zkr files are not in the
-    # reference checkout)
-    program_mode = args.circuit == "recursion" and not args.witness
 
     def prove_witness(slot):
         return r.prove_segment(hal, args.circuit, args.po2, dc, dd, da, globs[slot], version=version)
@@ -215,13 +246,14 @@ def main():
                                     bigint_records=t_.bigint_records()))
             traces.append(t_)
         trace = traces[0]
-        cyc, tx = trace.arrays()
-        idx, off, val = trace.injector_arrays()
-        bi = trace.bigint_array()
-        rt = r.ResidentTrace(hal, args.po2, trace.global_words(), idx, off, val, cyc, tx, trace.table_split_cycle,
-                             bigint=bi if len(bi) else None)
-        bigint_records = trace.bigint_records() or None
-        del cyc, tx, idx, off, val
+        if args.full:  # trace 0 in device memory, for the resident_trace leg and the roofline's proofs
+            cyc, tx = trace.arrays()
+            idx, off, val = trace.injector_arrays()
+            bi = trace.bigint_array()
+            rt = r.ResidentTrace(hal, args.po2, trace.global_words(), idx, off, val, cyc, tx, trace.table_split_cycle,
+                                 bigint=bi if len(bi) else None)
+            bigint_records = trace.bigint_records() or None
+            del cyc, tx, idx, off, val
         print(f"rank {rank}: {len(tjobs)} {args.guest} traces built in {time.perf_counter() - t0:.1f} s (trace 0: "
               f"{tjobs[0].table_split} rows before the tables, {tjobs[0].txns.size} memory transactions, "
               f"{tjobs[0].h2d_bytes() / 1e6:.0f} MB to upload)", file=sys.stderr)
@@ -293,16 +325,20 @@ def main():
         pipeline([tjobs[i % len(tjobs)] for i in range(max(args.warmup, k + 1))])  # warm every set, thread, pool
         _t, t = timed_segments(pipeline, [batch], 0, hal.synchronize, dist)
         seal, mix = out["res"][0]  # job 0 proved trace 0
+        last_seal, last_mix = out["res"][-1]  # the last timed step's
         seals_distinct = len({sl.tobytes() for sl, _ in out["res"]})
         verify_ms = sum(out["verify_ms"]) / len(out["verify_ms"])
-        t0 = time.perf_counter()
-        pipeline([tjobs[0]])
-        t_one = time.perf_counter() - t0
-        # the one segment's latency, split: the prover's share (upload wait, witness generation,
-        # accumulation, proof, seal to host), the receipt check after it, the rest (call set-up:
-        # trace sets, threads; the Python wrapper)
-        one_split = {"prove_ms": round(out["prove_ms"][0], 2), "verify_ms": round(out["verify_ms"][0], 2),
-                     "other_ms": round(1000.0 * t_one - out["prove_ms"][0] - out["verify_ms"][0], 2)}
+        one_seg = {}
+        if args.full:
+            t0 = time.perf_counter()
+            pipeline([tjobs[0]])
+            t_one = time.perf_counter() - t0
+            # the one segment's latency, split: the prover's share (upload wait, witness generation,
+            # accumulation, proof, seal to host), the receipt check after it, the rest (call set-up:
+            # trace sets, threads; the Python wrapper)
+            one_split = {"prove_ms": round(out["prove_ms"][0], 2), "verify_ms": round(out["verify_ms"][0], 2),
+                         "other_ms": round(1000.0 * t_one - out["prove_ms"][0] - out["verify_ms"][0], 2)}
+            one_seg = {"ms_one_segment_unpipelined": round(1000.0 * t_one, 1), "one_segment_split": one_split}
         rsteps = args.steps if args.resident_steps is None else args.resident_steps
         if rsteps > 0:
             t_r, seal_r, _ = timed_leg(lambda slot: r.prove_segment_trace_resident(hal, rt, bigint_records=bigint_records),
@@ -319,17 +355,26 @@ def main():
     elif program_mode:
         import itertools
         counter = itertools.count()
+        by_call = {}
 
         def prove_program(slot, j=None):
-            p = progs[next(counter) % len(progs) if j is None else j]
-            return r.prove_recursion(hal, args.po2, p["ctrl"], p["wom"], p["cycles"], p["iops"], p["seed"])
+            n = next(counter) if j is None else None
+            p = progs[n % len(progs) if j is None else j]
+            res = r.prove_recursion(hal, args.po2, p["ctrl"], p["wom"], p["cycles"], p["iops"], p["seed"])
+            if j is None:
+                by_call[n] = res  # call n proves program n mod len(progs), whichever thread takes it
+            return res
         t, _, _ = timed_leg(prove_program, "program")
+        last_seal, last_mix = by_call[max(by_call)]  # the last timed step's
         seal, mix = prove_program(0, 0)  # program 0's seal, for the CPU parity check
         program_valid = r.verify_seal("recursion", hal.suite, seal, check_validity=True) == args.po2
         if not args.no_prove_only:
             t_w, seal_w, _ = timed_leg(prove_witness, "prove_only")
     else:
         t, seal, mix = timed_leg(prove_witness, "prove")
+        last_seal, last_mix = seal, mix  # every step proves the rank's one witness
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, rank, last_seal, last_mix)
     mem = r.mem_stats()  # this rank's device footprint with k segments in flight
     # host-side gather of one seal digest per rank (the receipts stay on their hosts)
     digests = gather_results({rank: hashlib.sha256(seal.tobytes()).hexdigest()[:16]}, dist)
@@ -353,7 +398,7 @@ def main():
     cpu = None
     e2e = None
     acc_leg = None
-    if rank == 0:
+    if rank == 0 and args.full:
         prove_timed = ((lambda: r.prove_segment_trace_resident(hal, rt, bigint_records=bigint_records)) if trace_mode
                        else (lambda: prove_program(0, 0)) if program_mode else (lambda: prove_witness(0)))
         roofline = kernel_roofline(r, args, prove_timed, ms_per_step)
@@ -427,8 +472,7 @@ def main():
                            "distinct_seals_rank0": seals_distinct,
                            "h2d_bytes_per_segment": int(tjobs[0].h2d_bytes()),
                            "receipts_verified": not args.no_verify, "verify_ms_per_segment": round(verify_ms, 2),
-                           "ms_one_segment_unpipelined": round(1000.0 * t_one, 1),
-                           "one_segment_split": one_split} if trace_mode else {}),
+                           **one_seg} if trace_mode else {}),
                        **({"programs_per_rank": len(progs), "seal_valid_rank0": bool(program_valid)}
                           if program_mode else {}),
                        "ranks_share_devices": any(shared[i] for i in range(world))},

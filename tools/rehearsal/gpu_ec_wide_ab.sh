@@ -39,7 +39,7 @@ done
 for rep in $(seq 1 ${REPS:-2}); do
   for nm in $VARIANTS; do
     v=${nm%%=*}; sel $nm
-    timeout -k 10 300 python3 bench.py $BENCH > $O/bench_${v}_$rep.json 2> $O/bench_${v}_$rep.err || { tail -5 $O/bench_${v}_$rep.err; exit 1; }
+    timeout -k 10 300 python3 bench.py --full $BENCH > $O/bench_${v}_$rep.json 2> $O/bench_${v}_$rep.err || { tail -5 $O/bench_${v}_$rep.err; exit 1; }
     python3 -c "import json,sys; d=json.load(open('$O/bench_${v}_$rep.json')); print('$v', d['value'], d['ms_per_step'], (d.get('roofline') or {}).get('avg_launch_ms'), d['config']['seal_sha256_by_rank'])"
   done
 done

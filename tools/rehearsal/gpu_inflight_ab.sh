@@ -9,7 +9,7 @@ for rep in 1 2; do
     case $v in
       k3) env=""; k=3;; k4) env=""; k=4;; k4q8) env="GPU_MAX_HW_QUEUES=8"; k=4;; k3q8) env="GPU_MAX_HW_QUEUES=8"; k=3;;
     esac
-    env $env timeout -k 10 300 python3 -u bench.py $A --inflight $k > $O/$v.$rep.json 2> $O/$v.$rep.err || { tail -20 $O/$v.$rep.err; exit 1; }
+    env $env timeout -k 10 300 python3 -u bench.py --full $A --inflight $k > $O/$v.$rep.json 2> $O/$v.$rep.err || { tail -20 $O/$v.$rep.err; exit 1; }
     python3 -c "import json; d=json.load(open('$O/$v.$rep.json')); print('$v', $rep, d['ms_per_step'], d['value'])"
   done
 done

@@ -11,7 +11,7 @@ timeout -k 10 400 python -u -m pytest -x -q --timeout 200 --timeout-method threa
 tail -1 $O/pytest.log
 for v in new old; do
   sel $v
-  timeout -k 10 240 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_$v -o run -- python3 bench.py $REC --steps 8 --warmup 2 > $O/stats_$v.json 2> $O/stats_$v.err || { tail -5 $O/stats_$v.err; exit 1; }
+  timeout -k 10 240 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_$v -o run -- python3 bench.py --full $REC --steps 8 --warmup 2 > $O/stats_$v.json 2> $O/stats_$v.err || { tail -5 $O/stats_$v.err; exit 1; }
 done
 python3 - "$O" <<'PY'
 import csv, glob, sys
@@ -24,9 +24,9 @@ PY
 for rep in 1 2; do
   for v in new old; do
     sel $v
-    timeout -k 10 300 python3 bench.py $REC --steps 24 --warmup 6 > $O/rec_${v}_$rep.json 2> $O/rec_${v}_$rep.err || { tail -5 $O/rec_${v}_$rep.err; exit 1; }
+    timeout -k 10 300 python3 bench.py --full $REC --steps 24 --warmup 6 > $O/rec_${v}_$rep.json 2> $O/rec_${v}_$rep.err || { tail -5 $O/rec_${v}_$rep.err; exit 1; }
     python3 -c "import json; d=json.load(open('$O/rec_${v}_$rep.json')); print('recursion', '$v', d['value'], d['ms_per_step'], d['config']['seal_sha256_by_rank'])"
-    timeout -k 10 300 python3 bench.py --hashfn sha-256 --steps 12 --warmup 3 --no-cpu-baseline --no-prove-only --e2e-steps 0 --accum-steps 0 --resident-steps 0 > $O/rv_${v}_$rep.json 2> $O/rv_${v}_$rep.err || { tail -5 $O/rv_${v}_$rep.err; exit 1; }
+    timeout -k 10 300 python3 bench.py --full --hashfn sha-256 --steps 12 --warmup 3 --no-cpu-baseline --no-prove-only --e2e-steps 0 --accum-steps 0 --resident-steps 0 > $O/rv_${v}_$rep.json 2> $O/rv_${v}_$rep.err || { tail -5 $O/rv_${v}_$rep.err; exit 1; }
     python3 -c "import json; d=json.load(open('$O/rv_${v}_$rep.json')); print('rv32im', '$v', d['value'], d['ms_per_step'], d['config']['seal_sha256_by_rank'])"
   done
 done

@@ -11,6 +11,6 @@ tail -1 $O/pytest.log
 L="--no-cpu-baseline --no-prove-only --e2e-steps 0 --accum-steps 0 --resident-steps 0"
 for v in on off on; do
   F=""; [ $v = off ] && F="--no-verify --per-op-steps 0"
-  timeout -k 10 300 python3 -u bench.py $L $F > $O/bench_verify_$v.json 2> $O/bench_verify_$v.err || { tail -20 $O/bench_verify_$v.err; exit 1; }
+  timeout -k 10 300 python3 -u bench.py --full $L $F > $O/bench_verify_$v.json 2> $O/bench_verify_$v.err || { tail -20 $O/bench_verify_$v.err; exit 1; }
   python3 -c "import json; d=json.load(open('$O/bench_verify_$v.json')); c=d['config']; p=d.get('per_op_abi') or {}; print('verify $v', d['value'], d['ms_per_step'], c['ms_one_segment_unpipelined'], c['verify_ms_per_segment'], p.get('ms_per_step'), p.get('seal_equal'), (p.get('host_phases_ms') or {}).get('queries'))"
 done
