@@ -164,7 +164,8 @@ R0_HD int32_t sredc(int64_t t) {
 }
 R0_HD int32_t smul(int32_t a, int32_t b) { return sredc(int64_t(a) * b); }
 // |x| < 0.5p + 60 (after sredc of an M_EXT output) or x canonical: x^7 with every
-// intermediate below 0.969p in magnitude (products at most 0.94 p^2)
+// intermediate below 0.969p in magnitude (products at most 0.94 p^2). The partial rounds
+// feed it up to 0.75p (p2b_sbox evaluates the same chain of bounds at compile time).
 R0_HD int32_t p2_sbox_s(int32_t x) {
   const int32_t x2 = smul(x, x);
   const int32_t x4 = smul(x2, x2);
@@ -216,10 +217,17 @@ R0_HD void p2_m_ext64s(const int32_t* x, int64_t* y) {
 // of y + rcs - 2^32 - m p), so adding rcs - 2^32 carries out and cancels. One full-rate
 // v_add_u32 replaces the 64-bit add of rc per cell (sredc_rc). |y + rcs - 2^32| < 110.6p, so
 // the output stays below 0.5p + 52.
+//
+// poseidon2_mix does not restore the Montgomery form in the middle: p2_partial_rounds (below)
+// maps a state scaled by sigma_4 to one scaled by sigma_4, so its rounds 4-7 continue the
+// chain from sigma_4 (rcs[96..191], k_end_s). poseidon2_mix_quad restores it (k_mid) and
+// restarts round 5 from sigma = R (rc, k_end).
 struct P2Scaled {
-  uint32_t rc[8 * 24];   // rounds 0-3 and 5-7 (round 4 uses kP2Full as it is)
+  uint32_t rc[8 * 24];   // rounds 0-3 and 5-7 restarted from R (round 4 uses kP2Full as it is)
   uint32_t k_mid, k_end;
-  uint32_t rcs[8 * 24];  // rc + (2^32 mod p) mod p, in [1, p], for sredc_rc
+  uint32_t rcs[8 * 24];  // rc + (2^32 mod p) mod p, in [1, p], for sredc_rc; rounds 4-7 continue from sigma_4
+  uint32_t sigma_mid;    // sigma_4
+  uint32_t k_end_s;      // R^3 / sigma_8 of the continued chain
 };
 constexpr uint32_t p2c_mul(uint32_t a, uint32_t b) { return uint32_t(uint64_t(a) * b % kP); }
 constexpr uint32_t p2c_pow(uint32_t a, uint64_t e) {
@@ -246,13 +254,23 @@ constexpr P2Scaled p2_make_scaled() {
     }
     const uint32_t k = p2c_mul(R3, p2c_pow(sigma, kP - 2));
     if (half) t.k_end = k;
-    else t.k_mid = k;
+    else t.k_mid = k, t.sigma_mid = sigma;
   }
   for (int i = 0; i < 24; i++) t.rc[4 * 24 + i] = full[4 * 24 + i];
-  for (int i = 0; i < 8 * 24; i++) {
+  for (int i = 0; i < 4 * 24; i++) {
     const uint32_t v = uint32_t((uint64_t(t.rc[i]) + R) % kP);
     t.rcs[i] = v ? v : kP;
   }
+  uint32_t sigma = t.sigma_mid;
+  for (int r = 4; r < 8; r++) {
+    const uint32_t s = p2c_mul(sigma, Rinv);
+    for (int i = 0; i < 24; i++) {
+      const uint32_t v = uint32_t((uint64_t(p2c_mul(full[r * 24 + i], s)) + R) % kP);
+      t.rcs[r * 24 + i] = v ? v : kP;
+    }
+    sigma = p2c_mul(p2c_pow(s, 7), Rm6);
+  }
+  t.k_end_s = p2c_mul(R3, p2c_pow(sigma, kP - 2));
   return t;
 }
 // sredc(y + rc) (mod p) for the stored round constant rcs = rc + (2^32 mod p): above
@@ -265,6 +283,225 @@ __constant__ static const P2Scaled kP2S = p2_make_scaled();
 #else
 static constexpr P2Scaled kP2S = p2_make_scaled();
 #endif
+
+// ---- partial rounds as a block-linear map -------------------------------------------
+// Only cell 0 passes the S-box and M_INT = J + diag(d) is linear, so the 23 passive cells
+// stay untouched over a block of K = 7 rounds. With v_1..v_23 the cells at the block's
+// start, u_j the S-box output of round j and S_j the cell sum M_INT adds in round j:
+//   S_j     = u_j + sum_i d_i^j v_i + sum_{l<j} D_{j-1-l} S_l     (D_m = sum_{i>=1} d_i^m)
+//   z_{j+1} = S_j + d_0 u_j + rc_{j+1}                            (next S-box input)
+//   c_i     = d_i^K v_i + sum_{l<K} d_i^{K-1-l} S_l  (i >= 1),  c_0 = S_{K-1} + d_0 u_{K-1}
+// Every product is a 32-bit value times a compile-time constant centred into (-p/2, p/2],
+// accumulated in 64 bits: about 28 mads, three folds and two REDCs per round, and 8 mads, a
+// fold and a REDC per cell per block, where the round-by-round form spends 48 mads and 24
+// REDCs per round.
+//
+// Scales: the block takes and returns the passive cells as 64-bit values y_i = X_i sigma
+// (sigma = sigma_4, whatever the full rounds left; it only enters the constants), reads them
+// as v_i = sredc(y_i) = X_i sigma / R, and keeps z, u and s_j = sredc(..) = S_j R in
+// Montgomery form, so the S-box needs no scaling and all three blocks share their constants.
+// The last block's y feed round 4's sredc_rc directly.
+//
+// Bounds: sfold brings any int64 to at most 2^59 in magnitude (hi * (2^32 mod p) + lo), after
+// which sredc returns below 2^27 + p/2 + 1 = 0.567p. An accumulator is folded before its
+// worst case, the sum of |constant| * |input bound| over its terms, can pass 2^63, and
+// before every sredc. P2PartialBounds evaluates each worst case from the actual constants;
+// the static_asserts below it are the proof.
+constexpr int kP2K = 7;                       // rounds per block
+constexpr int kP2Seg0 = 9, kP2Seg1 = 18;      // an S_j row folds before v_9 and before v_18
+constexpr int32_t p2c_centre(uint32_t a) { return a > kP / 2 ? int32_t(a - kP) : int32_t(a); }
+struct P2Partial {
+  int32_t ct[24][kP2K + 1];  // S_j row: ct[i][j] = d_i^j R^2 / sigma' on v_i (sigma' = sigma / R; row 0 and [i][K] unused)
+  int32_t co[24][kP2K + 1];  // output row of cell i: co[i][m] = d_i^m sigma' on s_{K-1-m}, co[i][K] = d_i^K R on v_i
+  int32_t cd[kP2K - 1];      // D_m R on s_{j-1-m}
+  int32_t cu;                // R on u_j
+  int32_t cz;                // d_0 R on u_j, for z_{j+1}
+  int32_t k_in;              // R^2 / sigma': v_0 -> z_0
+  int32_t k_out;             // sigma': z -> y_0 after the last block
+  uint32_t rcz[22];          // rc_r R + (2^32 mod p) mod p in [1, p] for sredc_rc; [21] adds nothing
+};
+constexpr P2Partial p2_make_partial() {
+  P2Partial t{};
+  const uint32_t diag[24] = P2_DIAG_MONT, prc[21] = P2_PARTIAL_RC_MONT;
+  const uint32_t R = uint32_t((uint64_t(1) << 32) % kP), Rinv = p2c_pow(R, kP - 2);
+  const uint32_t sp = p2c_mul(p2_make_scaled().sigma_mid, Rinv), spinv = p2c_pow(sp, kP - 2);
+  const uint32_t R2sp = p2c_mul(p2c_mul(R, R), spinv);
+  uint32_t D[kP2K] = {};
+  for (int i = 1; i < 24; i++) {
+    const uint32_t d = p2c_mul(diag[i], Rinv);
+    uint32_t dm = 1;  // d^m
+    for (int m = 0; m <= kP2K; m++) {
+      if (m < kP2K) {
+        t.ct[i][m] = p2c_centre(p2c_mul(dm, R2sp));
+        t.co[i][m] = p2c_centre(p2c_mul(dm, sp));
+        D[m] = (D[m] + dm) % kP;
+      } else {
+        t.co[i][m] = p2c_centre(p2c_mul(dm, R));
+      }
+      dm = p2c_mul(dm, d);
+    }
+  }
+  for (int m = 0; m < kP2K - 1; m++) t.cd[m] = p2c_centre(p2c_mul(D[m], R));
+  t.cu = p2c_centre(R);
+  t.cz = p2c_centre(diag[0]);
+  t.k_in = p2c_centre(R2sp);
+  t.k_out = p2c_centre(sp);
+  for (int r = 0; r < 22; r++) {
+    const uint32_t v = uint32_t((uint64_t(r < 21 ? p2c_mul(prc[r], R) : 0u) + R) % kP);
+    t.rcz[r] = v ? v : kP;
+  }
+  return t;
+}
+#if defined(__HIP_DEVICE_COMPILE__)
+__constant__ static const P2Partial kP2L = p2_make_partial();
+#else
+static constexpr P2Partial kP2L = p2_make_partial();
+#endif
+
+// acc + a * c for a constant c. The constant is a scalar operand (an SGPR the compiler fills
+// with s_mov or s_load; smad64 would spend a v_mov per constant to put it in a VGPR). The
+// unused carry goes to vcc: an SGPR pair of its own per mad crowds out the constants.
+R0_HD int64_t smadc(int32_t a, int32_t c, int64_t acc) {
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(P2_NO_ASM)
+  int64_t r;
+  asm("v_mad_i64_i32 %0, vcc, %1, %2, %3" : "=v"(r) : "v"(a), "s"(c), "v"(acc) : "vcc");
+  return r;
+#else
+  return int64_t(a) * c + acc;
+#endif
+}
+R0_HD int64_t smulc(int32_t a, int32_t c) {  // a * c: the same mad with the inline constant 0
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(P2_NO_ASM)
+  int64_t r;
+  asm("v_mad_i64_i32 %0, vcc, %1, %2, 0" : "=v"(r) : "v"(a), "s"(c) : "vcc");
+  return r;
+#else
+  return int64_t(a) * c;
+#endif
+}
+// hi * (2^32 mod p) + lo with hi signed and lo unsigned: congruent to t, at most 2^59 in magnitude
+constexpr int32_t kFoldCs = int32_t(kFoldC);
+R0_HD int64_t sfold(int64_t t) {
+  return smadc(int32_t(uint32_t(uint64_t(t) >> 32)), kFoldCs, int64_t(uint64_t(uint32_t(uint64_t(t)))));
+}
+
+constexpr uint64_t kSredcMax = (uint64_t(1) << 63) - (uint64_t(kP) << 31) - 1;  // sredc: |t| + 2^31 p < 2^63
+constexpr uint64_t kAccMax = (uint64_t(1) << 63) - 1;
+constexpr uint64_t kSfoldOut = (uint64_t(1) << 31) * kFoldC + (uint64_t(1) << 32);  // |sfold(t)| <= this = 2^59
+constexpr uint64_t kP2YIn = uint64_t(1) << 38;  // |y| entering the partial rounds: M_EXT of |x| < 2^31, 112 * 2^31
+constexpr uint64_t p2b_add(uint64_t a, uint64_t b) { return a + b < a ? ~uint64_t(0) : a + b; }  // saturating
+constexpr uint64_t p2b_abs(int32_t c) { return c < 0 ? uint64_t(-int64_t(c)) : uint64_t(c); }
+constexpr uint64_t p2b_max(uint64_t a, uint64_t b) { return a > b ? a : b; }
+// |sredc(t)| for |t| <= T: (|t| + 2^31 p) / 2^32, rounded up; everything if sredc's own limit is passed
+constexpr uint64_t p2b_sredc(uint64_t T) {
+  return T > kSredcMax ? ~uint64_t(0) : ((T + (uint64_t(kP) << 31)) >> 32) + 1;
+}
+constexpr uint64_t p2b_smul(uint64_t a, uint64_t b) {
+  return (a >> 32) || (b >> 32) ? ~uint64_t(0) : p2b_sredc(a * b);
+}
+constexpr uint64_t p2b_sbox(uint64_t x) {  // |p2_sbox_s(x)| for |x| <= x
+  const uint64_t x2 = p2b_smul(x, x), x4 = p2b_smul(x2, x2), x6 = p2b_smul(x4, x2);
+  return p2b_smul(x6, x);
+}
+struct P2PartialBounds {
+  uint64_t v, s, u, z;  // |v_i|, |s_j|, |u_j|, |z_j| (as int32 values)
+  uint64_t u_next;      // the bound on u that follows from u: at most u (the invariant)
+  uint64_t acc;         // largest accumulator before a fold
+  uint64_t redc;        // largest argument of a REDC
+  uint64_t y0;          // |y_0| leaving the last block
+};
+constexpr P2PartialBounds p2_partial_bounds() {
+  const P2Partial t = p2_make_partial();
+  P2PartialBounds b{};
+  b.v = p2b_sredc(p2b_max(kP2YIn, kSfoldOut));
+  b.s = p2b_sredc(kSfoldOut);
+  // z = sredc_rc(sfold(..) + u cz, rcz) and u = sbox(z): u <= p holds first (z_0 below) and is kept
+  const uint64_t z_from_p = p2b_sredc(kSfoldOut + uint64_t(kP) * p2b_abs(t.cz) + (uint64_t(1) << 32));
+  const uint64_t z0_arg = b.v * p2b_abs(t.k_in) + (uint64_t(1) << 32);
+  b.u = p2b_max(p2b_sbox(z_from_p), p2b_sbox(p2b_sredc(z0_arg)));
+  b.redc = p2b_max(kSfoldOut + b.u * p2b_abs(t.cz) + (uint64_t(1) << 32), z0_arg);  // z_{j+1} and z_0
+  b.z = p2b_max(p2b_sredc(kSfoldOut + b.u * p2b_abs(t.cz) + (uint64_t(1) << 32)), p2b_sredc(z0_arg));
+  b.u_next = p2b_sbox(b.z);
+  for (int j = 0; j < kP2K; j++) {
+    uint64_t a = 0;
+    for (int i = 1; i < 24; i++) {
+      if (i == kP2Seg0 || i == kP2Seg1) b.acc = p2b_max(b.acc, a), a = kSfoldOut;
+      a = p2b_add(a, p2b_abs(t.ct[i][j]) * b.v);
+    }
+    for (int l = 0; l < j; l++) a = p2b_add(a, p2b_abs(t.cd[j - 1 - l]) * b.s);
+    a = p2b_add(a, p2b_abs(t.cu) * b.u);
+    b.acc = p2b_max(b.acc, a);
+  }
+  for (int i = 1; i < 24; i++) {
+    uint64_t a = p2b_abs(t.co[i][kP2K]) * b.v;
+    for (int m = 0; m < kP2K; m++) a = p2b_add(a, p2b_abs(t.co[i][m]) * b.s);
+    b.acc = p2b_max(b.acc, a);
+  }
+  b.y0 = b.z * p2b_abs(t.k_out);
+  return b;
+}
+constexpr P2PartialBounds kP2LB = p2_partial_bounds();
+static_assert(kP2LB.v < (uint64_t(1) << 31) && kP2LB.s < (uint64_t(1) << 31), "v_i and s_j fit int32");
+static_assert(kP2LB.u <= kP && kP2LB.u_next <= kP2LB.u, "|u| <= kP2LB.u is kept from round to round");
+static_assert(kP2LB.z < (uint64_t(1) << 31) && p2b_sbox(kP2LB.z) <= kP, "z fits the S-box");
+static_assert(kP2LB.acc <= kAccMax, "no accumulator passes 2^63 before its fold");
+static_assert(kP2LB.redc <= kSredcMax && kSfoldOut <= kSredcMax, "every REDC argument is within sredc's limit");
+// round 4 reads the last block's y through sredc_rc (rcs <= p < 2^32) and p2_sbox_s
+static_assert(p2b_sbox(p2b_sredc(p2b_max(kP2LB.y0, kSfoldOut) + (uint64_t(1) << 32))) <= kP, "round 4 input");
+
+// y[24]: the state times sigma (mod p), |y_i| <= 2^38 -> the state 21 partial rounds later,
+// times sigma, |y_i| <= max(kSfoldOut, kP2LB.y0) < 2^61
+R0_HD void p2_partial_rounds(int64_t* y) {
+  int32_t v[24], s[kP2K];
+  int32_t z = sredc_rc(smulc(sredc(y[0]), kP2L.k_in), kP2L.rcz[0]);
+#pragma unroll 1
+  for (int b = 0; b < 21 / kP2K; b++) {
+    // Read the block's constants at an offset (0) the compiler cannot see through: loads
+    // from a known __constant__ address are hoisted out of this loop and the caller's, and
+    // ~200 hoisted constants spill from SGPRs to VGPR lanes (a v_readlane per use).
+    uint32_t o = 0;
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm volatile("" : "+s"(o));
+#endif
+    const P2Partial* t = &kP2L + o;
+#pragma unroll
+    for (int i = 1; i < 24; i++) v[i] = sredc(y[i]);
+    // the passive cells' share of every S_j first, cell by cell: seven independent chains
+    // (a v_mad_i64_i32 that reads the one before it waits a cycle) and one run of constants per cell
+    int64_t a[kP2K];
+#pragma unroll
+    for (int i = 1; i < 24; i++) {
+#pragma unroll
+      for (int j = 0; j < kP2K; j++) {
+        if (i == kP2Seg0 || i == kP2Seg1) a[j] = sfold(a[j]);
+        a[j] = i == 1 ? smulc(v[i], t->ct[i][j]) : smadc(v[i], t->ct[i][j], a[j]);
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < kP2K; j++) {
+      const int32_t u = p2_sbox_s(z);
+      int64_t f = a[j];
+#pragma unroll
+      for (int l = 0; l < j; l++) f = smadc(s[l], t->cd[j - 1 - l], f);
+      f = sfold(smadc(u, t->cu, f));
+      s[j] = sredc(f);
+      z = sredc_rc(smadc(u, t->cz, f), t->rcz[b * kP2K + j + 1]);
+    }
+#pragma unroll
+    for (int i = 1; i < 24; i += 2) {  // two cells' chains interleaved
+      const int i1 = i + 1 < 24 ? i + 1 : i;
+      int64_t f0 = smulc(v[i], t->co[i][kP2K]), f1 = smulc(v[i1], t->co[i1][kP2K]);
+#pragma unroll
+      for (int l = 0; l < kP2K; l++) {
+        f0 = smadc(s[l], t->co[i][kP2K - 1 - l], f0);
+        if (i1 != i) f1 = smadc(s[l], t->co[i1][kP2K - 1 - l], f1);
+      }
+      y[i] = sfold(f0);
+      if (i1 != i) y[i1] = sfold(f1);
+    }
+  }
+  y[0] = smulc(z, kP2L.k_out);  // rcz[21] added nothing: z is cell 0 in Montgomery form
+}
 
 R0_HD void poseidon2_mix(uint32_t* c) {
   int64_t y[24];
@@ -282,38 +519,18 @@ R0_HD void poseidon2_mix(uint32_t* c) {
     for (int i = 0; i < 24; i++) x[i] = p2_sbox_s(sredc_rc(y[i], kP2S.rcs[r * 24 + i]));
     p2_m_ext64s(x, y);
   }
-#pragma unroll
-  for (int i = 0; i < 24; i++) c[i] = s_canon(smul(sredc(y[i]), int32_t(kP2S.k_mid)));
-#pragma unroll
-  // Partial rounds keep every cell lazy in [0, 2p): with cells c < X the M_INT output
-  // REDC(c*d + sf) < 0.469 X + sf/2^32 + p, whose fixed point (sf < 2^57 + 2^32 after
-  // two folds) is 3.86e9 < 2p < 2^32, so nothing is canonicalised until the end. The
-  // sum is two 12-term halves (12 * 2p * (2^32 mod p) < 2^64).
-  for (int r = 0; r < 21; r++) {
-    c[0] = p2_sbox_lazy(fp_add(umin(c[0], c[0] - kP), kP2Partial[r]));
-    uint64_t s0 = 0, s1 = 0;
-#pragma unroll
-    for (int i = 0; i < 12; i++) {  // two interleaved chains: no dependent back-to-back mads
-      s0 = mad64(c[i], kFoldC, s0);
-      s1 = mad64(c[12 + i], kFoldC, s1);
-    }
-    const uint64_t sf = fold64(fold64(s0) + fold64(s1));
-#pragma unroll
-    for (int i = 0; i < 24; i++) c[i] = mont_lazy(uint64_t(c[i]) * kP2Diag[i] + sf);
-  }
-#pragma unroll
-  for (int i = 0; i < 24; i++) c[i] = umin(c[i], c[i] - kP);
-#pragma unroll
-  for (int i = 0; i < 24; i++) x[i] = p2_sbox_s(int32_t(fp_add(c[i], kP2Full[4 * 24 + i])));
-  p2_m_ext64s(x, y);
+  // The partial rounds keep the scale sigma_4 (p2_partial_rounds), so rounds 4-7 go on as
+  // rounds 1-3 do, with constants scaled along the continued chain; round 4's input is
+  // below 0.57p in magnitude (static_assert above), within the S-box's range.
+  p2_partial_rounds(y);
 #pragma unroll 1
-  for (int r = 5; r < 8; r++) {
+  for (int r = 4; r < 8; r++) {
 #pragma unroll
     for (int i = 0; i < 24; i++) x[i] = p2_sbox_s(sredc_rc(y[i], kP2S.rcs[r * 24 + i]));
     p2_m_ext64s(x, y);
   }
 #pragma unroll
-  for (int i = 0; i < 24; i++) c[i] = s_canon(smul(sredc(y[i]), int32_t(kP2S.k_end)));
+  for (int i = 0; i < 24; i++) c[i] = s_canon(smul(sredc(y[i]), int32_t(kP2S.k_end_s)));
 }
 
 #if defined(__HIP__)
