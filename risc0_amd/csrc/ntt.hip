@@ -310,7 +310,8 @@ __global__ __launch_bounds__(NT) void ntt_pass_kernel(PassArgs p) {
     for (uint32_t i = 0; i < E; i++) lds[lidx<COLS, B, C>(j, R * i + t0)] = r[i];
   }
   __syncthreads();
-  if (!INV) stages<false, COLS, B, C, (EB < B ? EB : 0), NT>(lds, tw, compact);
+  // EB == B (one input word per row, replicated above): no stage is left, the row is 2^B copies
+  if (!INV) stages<false, COLS, B, C, EB, NT>(lds, tw, compact);
   else stages<true, COLS, B, C, 0, NT>(lds, tw);
   // ---- store (inverse column passes post-scale; last inverse pass normalises) ----
   if constexpr (COLS && B >= 8 - C) {

@@ -17,7 +17,7 @@ import sys
 import numpy as np
 import pytest
 
-import ir_eval
+from ec_extreme import MODES, enc, extreme_inputs, reference
 from test_golden import GOLD, INDEX, e_mul, e_pow, eval_inputs, rou_fwd
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -51,10 +51,6 @@ def host_ec(request, tmp_path_factory):
 
 def ptr(a):
     return a.ctypes.data_as(u32p)
-
-
-def enc(x):
-    return np.array([(int(v) % P) * 2**32 % P for v in x], dtype=np.uint32)
 
 
 def run_host(lib, circuit, args_plain_words, poly_mix, po2):
@@ -102,29 +98,12 @@ def test_generated_eval_check_matches_golden(host_ec, oracle, case):
 
 
 @pytest.mark.parametrize("circuit", ["rv32im", "recursion"])
-@pytest.mark.parametrize("mode", ["all_pm1", "edge_mix"])
+@pytest.mark.parametrize("mode", MODES)
 def test_generated_eval_check_extreme_inputs(host_ec, oracle, circuit, mode):
     po2 = 2
-    D = 4 << po2
     d = oracle.load_circuit_json(circuit)
-    rng = np.random.default_rng(7)
-    gs = d["group_sizes"]
-    sizes = {"accum": gs[0] * D, "code": gs[1] * D, "data": gs[2] * D, "mix": d["mix_size"],
-             "global": d["output_size"]}
-    edge = np.array([0, 1, 2, P - 2, P - 1], dtype=np.uint64)
-    plain = {}
-    for k, n in sizes.items():
-        plain[k] = np.full(n, P - 1, np.uint64) if mode == "all_pm1" else rng.choice(edge, size=n)
-    poly_mix = (P - 1, P - 1, P - 1, P - 1) if mode == "all_pm1" else (P - 2, 1, P - 1, 2)
+    plain, poly_mix = extreme_inputs(d, mode, po2)
     args_plain = [plain[a] for a in d["eval_args"]]
     out = run_host(host_ec[circuit], circuit, [enc(a) for a in args_plain], poly_mix, po2)
-    pows = [e_pow(poly_mix, k) for k in d["poly_mix_powers"]]
-    fp = ir_eval.evaluate(ir_eval.load_ir(circuit), args_plain, D, pows)
-    w = rou_fwd()[po2 + 2]
-    ref = np.zeros((4, D), np.uint64)
-    for c in range(D):
-        x = 3 * pow(w, c, P) % P
-        inv = pow((pow(x, 1 << po2, P) - 1) % P, P - 2, P)
-        for k in range(4):
-            ref[k, c] = int(fp[k][c]) * inv % P
+    ref = reference(circuit, d, plain, poly_mix, po2)
     assert np.array_equal(out, enc(ref.reshape(-1)))
