@@ -169,9 +169,21 @@ typedef struct r0hip_bigint_back {
  * bigint accum"). Host-only. */
 const char* r0hip_rv32im_bigint_accum_states(const uint32_t* h_mix, const r0hip_bigint_back* h_backs, size_t n,
                                              size_t rows, uint32_t* h_states);
+/* The same states computed on the device (BigIntAccum::step, byte_poly.rs:381-470, as three
+ * parallel scans over the records: poly an affine scan, term a last-writer scan, total a
+ * segmented sum; EqZero checked per record): the n records are uploaded as they are and
+ * d_states (device memory) receives n x 12 words, in record order, equal to what the host
+ * function writes. n <= rows <= 2^26. Fails with the host function's messages, at the earliest
+ * record in trace order that fails any check. Always takes the device path; n == 0 is a no-op.
+ * Complete on return. */
+const char* r0hip_rv32im_bigint_accum_states_device(uint32_t* d_states, const uint32_t* h_mix,
+                                                    const r0hip_bigint_back* h_backs, size_t n, size_t rows);
 /* The states above scattered into accum columns 0..11 (BigIntAccumState::offsets,
  * byte_poly.rs:362-377) of each record's row of d_accum (column-major, `rows` rows): what
- * WitnessGenerator::accum does before step_accum (witgen/mod.rs:187-205). */
+ * WitnessGenerator::accum does before step_accum (witgen/mod.rs:187-205). From 4096 records
+ * on, the states are computed on the device (as r0hip_rv32im_bigint_accum_states_device) and
+ * scattered from device memory; below that the host loop is faster and its states are
+ * uploaded. The words and the errors are the same either way. */
 const char* r0hip_rv32im_bigint_accum_inject(uint32_t* d_accum, size_t rows, const uint32_t* h_mix,
                                              const r0hip_bigint_back* h_backs, size_t n);
 

@@ -263,6 +263,14 @@ unsafe extern "C" {
         rows: usize,
         h_states: *mut u32,
     ) -> *const c_char;
+    /// the same states computed on the device into d_states (n x 12 words), complete on return
+    pub fn r0hip_rv32im_bigint_accum_states_device(
+        d_states: *mut u32,
+        h_mix: *const u32,
+        h_backs: *const R0HipBigIntBack,
+        n: usize,
+        rows: usize,
+    ) -> *const c_char;
     pub fn r0hip_rv32im_bigint_accum_inject(
         d_accum: *mut u32,
         rows: usize,

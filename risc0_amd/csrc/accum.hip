@@ -109,12 +109,13 @@ __global__ __launch_bounds__(kT) void finalize_kernel(uint32_t* accum, uint64_t 
 }
 
 // BigInt accumulator states (bigint.cpp): record k's 12 words into accum columns 0..11 of its
-// row (BigIntAccumState::offsets, rv32im witgen/byte_poly.rs:362-377)
+// row (BigIntAccumState::offsets, rv32im witgen/byte_poly.rs:362-377); the row is
+// row_of[k * stride] (a row list, or the first word of each uploaded record)
 __global__ __launch_bounds__(kT) void bigint_scatter_kernel(uint32_t* accum, uint64_t rows, const uint32_t* row_of,
-                                                            const uint32_t* states, uint64_t n) {
+                                                            uint32_t stride, const uint32_t* states, uint64_t n) {
   const uint64_t k = uint64_t(blockIdx.x) * kT + threadIdx.x;
   if (k >= n) return;
-  const uint64_t row = row_of[k];
+  const uint64_t row = row_of[k * stride];
 #pragma unroll
   for (int c = 0; c < 12; c++) accum[uint64_t(c) * rows + row] = states[k * 12 + c];
 }
@@ -122,10 +123,10 @@ __global__ __launch_bounds__(kT) void bigint_scatter_kernel(uint32_t* accum, uin
 }  // namespace
 
 void bigint_scatter(hipStream_t s, uint32_t* accum, size_t rows, const uint32_t* d_rows, const uint32_t* d_states,
-                    size_t n) {
+                    size_t n, size_t row_stride) {
   if (n == 0) return;
   hipLaunchKernelGGL(bigint_scatter_kernel, dim3(div_up(n, kT)), dim3(kT), 0, s, accum, uint64_t(rows), d_rows,
-                     d_states, uint64_t(n));
+                     uint32_t(row_stride), d_states, uint64_t(n));
   HIP_OK(hipGetLastError());
 }
 

@@ -330,6 +330,15 @@ const char* r0hip_rv32im_bigint_accum_states(const uint32_t* h_mix, const r0hip_
     if (n) memcpy(h_states, st.data(), st.size() * 4);
   });
 }
+const char* r0hip_rv32im_bigint_accum_states_device(uint32_t* d_states, const uint32_t* h_mix,
+                                                    const r0hip_bigint_back* h_backs, size_t n, size_t rows) {
+  return wrap([&] {
+    if (n == 0) return;
+    R0_REQUIRE(h_mix && h_backs && d_states, "r0hip_rv32im_bigint_accum_states_device: null argument");
+    stage_reset();
+    rv32im_bigint_accum_states_device(stream(), d_states, h_mix, h_backs, n, rows);
+  });
+}
 const char* r0hip_rv32im_bigint_accum_inject(uint32_t* d_accum, size_t rows, const uint32_t* h_mix,
                                              const r0hip_bigint_back* h_backs, size_t n) {
   return wrap([&] {

@@ -98,6 +98,12 @@ enum ScratchSlot : int {
   kSlotAccTileSums = 62,
   kSlotBigIntRows = 63,
   kSlotBigIntStates = 64,
+  // BigInt accumulator scans (bigint.cpp, bigint_accum.hip): the uploaded records, each
+  // record's byte polynomial, the tile sums, the failing-EqZero word
+  kSlotBigIntBacks = 65,
+  kSlotBigIntDelta = 66,
+  kSlotBigIntTileSums = 67,
+  kSlotBigIntFail = 68,
   // recursion witness generation (recursion_witgen.hip): the uploaded preflight trace, the
   // exec runs, each cycle's first IOP value, hipcub temporary storage
   kSlotWitgenWom = 70,
@@ -266,11 +272,21 @@ struct AccumStep {
 // total), in record order; throws on an invalid EqZero as the reference does
 std::vector<uint32_t> rv32im_bigint_accum_states(const uint32_t* mix, const r0hip_bigint_back* backs, size_t n,
                                                  size_t rows);
+// The same states computed on the device into d_states (n x 12 words), complete on return, with
+// the host function's errors. Returns the records as uploaded (this thread's kSlotBigIntBacks).
+const r0hip_bigint_back* rv32im_bigint_accum_states_device(hipStream_t s, uint32_t* d_states, const uint32_t* mix,
+                                                           const r0hip_bigint_back* backs, size_t n, size_t rows);
+// the scans themselves (bigint_accum.hip) over n <= 2^26 records in device memory, every
+// poly_op in range; mix is on the host. *d_fail becomes the smallest index of a record whose
+// EqZero goal is nonzero, 0xFFFFFFFF if there is none.
+void bigint_accum_scan(hipStream_t s, uint32_t* d_states, const r0hip_bigint_back* d_backs, size_t n,
+                       const uint32_t* mix, uint32_t* d_fail);
 // the states scattered into accum columns 0..11 of each record's row (witgen/mod.rs:187-205)
 void rv32im_bigint_inject(hipStream_t s, uint32_t* accum, size_t rows, const uint32_t* mix,
                           const r0hip_bigint_back* backs, size_t n);
+// record k's row is d_rows[k * row_stride] (1: a row list; 7: the records themselves)
 void bigint_scatter(hipStream_t s, uint32_t* accum, size_t rows, const uint32_t* d_rows, const uint32_t* d_states,
-                    size_t n);
+                    size_t n, size_t row_stride = 1);
 // recursion circuit accumulation (recursion_accum.hip): compute, prefix product, verify
 void recursion_accum(hipStream_t s, const uint32_t* ctrl, const uint32_t* global, const uint32_t* data,
                      const uint32_t* mix, uint32_t* accum, size_t steps, size_t cycles);

@@ -93,6 +93,7 @@ def _declare(L):
         "r0hip_prove_segment_accum": [C.c_char_p, C.c_int, C.c_uint32, vp, vp, vp, sz, vp, sz, vp, C.c_int,
                                       C.c_uint32, u32p, sz, C.POINTER(sz), u32p],
         "r0hip_rv32im_bigint_accum_states": [u32p, vp, sz, sz, u32p],
+        "r0hip_rv32im_bigint_accum_states_device": [vp, u32p, vp, sz, sz],
         "r0hip_recursion_witgen": [vp, vp, vp, sz, u32p, sz, u32p, sz, u32p, sz],
         "r0hip_rv32im_witgen": [C.c_uint32, vp, vp, C.c_uint32],
         "r0hip_prove_segment_trace_resident": [C.c_int, C.c_uint32, C.c_uint32, vp, vp, sz, vp, vp, vp, vp, sz,
@@ -380,11 +381,22 @@ class BigIntBack(C.Structure):
     _fields_ = [("row", C.c_uint32), ("poly_op", C.c_uint32), ("coeff", C.c_uint32), ("bytes", C.c_uint8 * 16)]
 
 
+#: struct r0hip_bigint_back as a NumPy structured dtype (itemsize 28)
+BIGINT_BACK_DTYPE = np.dtype([("row", "<u4"), ("poly_op", "<u4"), ("coeff", "<u4"), ("bytes", "u1", (16,))])
+assert BIGINT_BACK_DTYPE.itemsize == C.sizeof(BigIntBack)
+
+
 def bigint_backs(records):
-    """ctypes array of BigIntBack from [(row, poly_op, coeff, bytes16), ...] (None/[] -> None)"""
+    """ctypes array of BigIntBack from [(row, poly_op, coeff, bytes16), ...] or from a
+    structured array of BIGINT_BACK_DTYPE, copied whole (None/empty -> None)"""
     if records is None or len(records) == 0:
         return None
     arr = (BigIntBack * len(records))()
+    if isinstance(records, np.ndarray):
+        assert records.dtype == BIGINT_BACK_DTYPE and records.ndim == 1, records.dtype
+        rec = np.ascontiguousarray(records)
+        C.memmove(arr, rec.ctypes.data, rec.nbytes)
+        return arr
     for a, (row, op, coeff, by) in zip(arr, records):
         a.row, a.poly_op, a.coeff = int(row), int(op), int(coeff)
         for i, b in enumerate(by):
@@ -402,6 +414,20 @@ def bigint_accum_states(mix, records, rows):
     check(lib().r0hip_rv32im_bigint_accum_states(mp, None if arr is None else C.cast(arr, C.c_void_p), n, rows,
                                                  out.ctypes.data_as(u32p)))
     return out[: n * 12].reshape(n, 12)
+
+
+def bigint_accum_states_device(hal, mix, records, rows):
+    """r0hip_rv32im_bigint_accum_states_device: the same states from the device's parallel scans
+    (always the device path); returns (len(records), 12) Montgomery words"""
+    arr = bigint_backs(records)
+    n = 0 if arr is None else len(arr)
+    m, mp = _h(mix)
+    out = hal.alloc_u32("bigint_states", n * 12)
+    check(lib().r0hip_rv32im_bigint_accum_states_device(out.ptr, mp, None if arr is None else C.cast(arr, C.c_void_p),
+                                                        n, rows))
+    st = out.to_numpy().reshape(n, 12)
+    out.free()
+    return st
 
 
 def bigint_accum_inject(accum, rows, mix, records):

@@ -20,7 +20,7 @@ FAMILIES = [
     (r"mix_kernel", "mix_poly_coeffs"),
     (r"div_", "poly_divide"),
     (r"rvwg::witgen_major_|bucket_count_kernel|bucket_fill_kernel|rocprim::", "rv32im_witgen"),
-    (r"rv_accum::|tile_sums_kernel|scan_sums_kernel|tile_scan_kernel|finalize_kernel|bigint_scatter_kernel",
+    (r"rv_accum::|tile_sums_kernel|scan_sums_kernel|tile_scan_kernel|finalize_kernel|bigint_scatter_kernel|bigint_delta_kernel",
      "rv32im_accum"),
 ]
 
