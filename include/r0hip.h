@@ -116,6 +116,14 @@ const char* r0hip_prefix_products(uint32_t* d_io, size_t count);
 /* not a reference symbol: synthetic witness words (uniform canonical BabyBear values from a
  * counter hash of seed and index) for benches and tests at full size */
 const char* r0hip_fill_uniform(uint32_t* d_out, size_t count, uint64_t seed);
+/* not a reference symbol: keyed noise words, the generator of r0hip_prove_recursion_keyed. The
+ * ChaCha20 keystream of RFC 8439 section 2.3 (20 rounds, 32-bit block counter starting at 0)
+ * under h_key (8 words) and h_nonce (3 words), both as the RFC's little-endian state words.
+ * Element i is the 128-bit little-endian integer made of keystream words 4i..4i+3, reduced
+ * mod p = 15 * 2^27 + 1 and stored as the raw word (bias below 2^-96), so block b yields
+ * elements 4b..4b+3 and the words do not depend on how the kernel is launched. count <= 2^34.
+ * The key is passed to the kernel by value: no device copy of it is made. */
+const char* r0hip_fill_chacha20(uint32_t* d_out, size_t count, const uint32_t* h_key, const uint32_t* h_nonce);
 
 /* ---- hashing (sppark_poseidon2_{rows,fold}, sppark_poseidon254_{rows,fold}, risc0_zkp_cuda_sha_{rows,fold};
  * sys/src/cuda.rs:49-72) ---- */
@@ -318,11 +326,28 @@ const char* r0hip_recursion_witgen(const uint32_t* d_ctrl, uint32_t* d_data, uin
  * last 1024 rows of data and accum (per-cell values of r0hip_fill_uniform(noise_seed) and
  * (noise_seed + 1), laid out as witgen.rs:101-158 copies its noise matrices), zeroize, then
  * r0hip_prove_segment_accum's sequence with work cycles = n_cycles. po2 >= 11 and n_cycles <=
- * 2^po2 - 1024 (program.rs:57). Seal and mix out as r0hip_prove_segment. */
+ * 2^po2 - 1024 (program.rs:57). Seal and mix out as r0hip_prove_segment.
+ * DETERMINISTIC, for tests and benches: the noise is a counter hash of the 64-bit noise_seed,
+ * not a random draw, so a seal made by this call is not zero-knowledge. The call to ship is
+ * r0hip_prove_recursion_keyed below. */
 const char* r0hip_prove_recursion(int suite, uint32_t po2, const uint32_t* d_ctrl, const uint32_t* h_wom, size_t n_wom,
                                   const uint32_t* h_cycles, size_t n_cycles, const uint32_t* h_iops, size_t n_iops,
                                   uint64_t noise_seed, uint32_t* h_seal, size_t seal_cap, size_t* seal_len,
                                   uint32_t* h_mix_out);
+/* The same sequence with the ZK noise drawn from a keyed ChaCha20 stream on the device
+ * (r0hip_fill_chacha20), as the reference draws it from its OS-seeded CSPRNG (circuit/recursion/
+ * src/prove/witgen.rs:103-105, 146-149). The data noise matrix is the stream of h_key with nonce
+ * {0, lo32(stream_id), hi32(stream_id)}, the accum noise matrix the one with nonce {1, lo32,
+ * hi32}; element i of a stream is word i of the cols x 1024 noise buffer, where
+ * r0hip_prove_recursion puts word i of its generator. h_key: 8 words, or NULL for 32 bytes of
+ * getrandom(2) drawn for this call (the call fails if the OS gives none; there is no weaker
+ * source). A caller's key must never meet the same stream_id twice. Host copies of the key are
+ * wiped when the call returns. */
+const char* r0hip_prove_recursion_keyed(int suite, uint32_t po2, const uint32_t* d_ctrl, const uint32_t* h_wom,
+                                        size_t n_wom, const uint32_t* h_cycles, size_t n_cycles,
+                                        const uint32_t* h_iops, size_t n_iops, const uint32_t* h_key,
+                                        uint64_t stream_id, uint32_t* h_seal, size_t seal_cap, size_t* seal_len,
+                                        uint32_t* h_mix_out);
 
 /* ---- segment pipeline (r0vm's per-GPU worker queue, r0vm/src/actors/worker.rs:75-76, over the
  * zkvm's per-segment prove loop, zkvm/src/host/server/prove/prover_impl.rs:84-94) ----
@@ -391,6 +416,78 @@ typedef struct r0hip_trace_job {
 } r0hip_trace_job;
 const char* r0hip_prove_trace_segments(int suite, uint32_t po2, r0hip_trace_job* jobs, size_t njobs,
                                        uint32_t in_flight, int verify);
+
+/* ---- the GPU worker: a persistent queue of mixed jobs (r0vm's GPU actor, r0vm/src/actors/
+ * worker.rs:165, 289-312: tasks arrive one at a time, ProveSegmentCore interleaved with Lift and
+ * Join) ----
+ * r0hip_worker_create starts an uploader thread, in_flight prover threads and, with verify != 0,
+ * a verifier thread, each with its own stream, pool and staging, and allocates in_flight + 1
+ * device sets sized for max_po2 (2..24). The calling thread proves nothing. With in_flight <= 3
+ * the uploader and the provers fit the 4 hardware queues HIP opens by default. h_noise_key: the
+ * 8-word ChaCha20 key of the recursion jobs' ZK noise; NULL draws 32 bytes of getrandom(2) for
+ * the worker's lifetime (create fails if the OS gives none). A caller's key makes runs
+ * reproducible and is FOR TESTS ONLY: a key reused across workers repeats nonces.
+ * r0hip_worker_submit checks what needs no device (the kind, the suite, po2 <= max_po2, for a
+ * recursion job po2 >= 11 and n_cycles <= 2^po2 - 1024, null pointers); a failure returns an
+ * error and queues nothing. Otherwise it clears the job's out fields, assigns job->ticket (the
+ * submission number, from 0), appends the job to a FIFO and returns without touching the GPU.
+ * Jobs start in ticket order. The job struct and every host array it names must stay valid
+ * until r0hip_worker_wait hands the job back.
+ * Per job: rv32im jobs (kind R0HIP_JOB_RV32IM_TRACE) are staged and proved as
+ * r0hip_prove_trace_segments proves them, at the job's own po2; their seals equal
+ * r0hip_prove_segment_trace's. Recursion jobs (R0HIP_JOB_RECURSION) take the control group from
+ * host memory (staged by the uploader) and are proved as r0hip_prove_recursion_keyed proves
+ * them with the worker's key and stream_id = the job's ticket, so the seal equals that call's on
+ * the same inputs. A job's own failure goes to job->error (malloc'd, free() it) and the other
+ * jobs continue. With verify, every seal goes through r0hip_verify_seal (recursion: against the
+ * job's h_code_roots allow-list); a failed check sets "receipt verification failed: ..." on
+ * that job alone.
+ * r0hip_worker_wait returns the next finished job in completion order, each job exactly once.
+ * *done = NULL with no error: the timeout passed (timeout_ms = 0 polls, < 0 waits without
+ * limit) or nothing is outstanding; it never blocks when nothing is outstanding.
+ * r0hip_worker_destroy runs everything submitted to completion (jobs not yet waited for keep
+ * their results in their structs), joins the threads and returns the device memory: after
+ * r0hip_trim, r0hip_mem_stats' live bytes are what they were before r0hip_worker_create.
+ * submit and wait may be called from different threads; destroy must be the last call. */
+typedef struct r0hip_worker r0hip_worker;
+#define R0HIP_JOB_RV32IM_TRACE 0
+#define R0HIP_JOB_RECURSION 1
+typedef struct r0hip_recursion_input {
+  const uint32_t* h_ctrl;        /* control group, 23 columns x 2^po2, host */
+  const uint32_t* h_wom;         /* as r0hip_recursion_witgen takes them */
+  size_t n_wom;
+  const uint32_t* h_cycles;
+  size_t n_cycles;
+  const uint32_t* h_iops;
+  size_t n_iops;
+  const uint32_t* h_code_roots;  /* allow-list for the receipt check, 8 words each */
+  size_t n_code_roots;           /* 0 = none */
+} r0hip_recursion_input;
+typedef struct r0hip_worker_job {
+  uint32_t kind;                      /* R0HIP_JOB_* */
+  int suite;
+  uint32_t po2;
+  r0hip_trace_input trace;            /* kind 0 */
+  const r0hip_bigint_back* h_bigint;  /* kind 0: the trace's BigInt backs (NULL, 0 if none) */
+  size_t n_bigint;
+  r0hip_recursion_input recursion;    /* kind 1 */
+  void* user;                         /* untouched */
+  uint32_t* h_seal;                   /* out: the seal (seal_cap words), its length in seal_len */
+  size_t seal_cap;
+  size_t seal_len;
+  uint32_t* h_mix_out;                /* out (optional): the mix words (36 rv32im, 20 recursion) */
+  const char* error;                  /* out: NULL or a malloc'd message (free() it) */
+  int verified;                       /* out: 1 when the seal passed r0hip_verify_seal */
+  double verify_ms;                   /* out: host milliseconds of that check */
+  double prove_ms;                    /* out: host milliseconds from a prover taking the job to its
+                                         seal in host memory (the wait for its upload included) */
+  uint64_t ticket;                    /* out: submission number, from 0 */
+} r0hip_worker_job;
+const char* r0hip_worker_create(r0hip_worker** out, uint32_t max_po2, uint32_t in_flight, int verify,
+                                const uint32_t* h_noise_key);
+const char* r0hip_worker_submit(r0hip_worker* w, r0hip_worker_job* job);
+const char* r0hip_worker_wait(r0hip_worker* w, r0hip_worker_job** done, int64_t timeout_ms);
+const char* r0hip_worker_destroy(r0hip_worker* w);
 
 /* ---- seal verification (risc0/zkp/src/verify/mod.rs:500-560 `verify`, with merkle.rs:79-186,
  * fri.rs:36-155, read_iop.rs:20-84; rv32im seals lead with the version word 2,

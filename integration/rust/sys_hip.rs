@@ -81,6 +81,55 @@ pub struct R0HipTraceJob {
     pub prove_ms: f64,
 }
 
+/// The GPU worker's handle (struct r0hip_worker): opaque, made by r0hip_worker_create.
+#[repr(C)]
+pub struct R0HipWorker {
+    _private: [u8; 0],
+}
+
+/// Job kinds of R0HipWorkerJob (R0HIP_JOB_*).
+pub const R0HIP_JOB_RV32IM_TRACE: u32 = 0;
+pub const R0HIP_JOB_RECURSION: u32 = 1;
+
+/// One recursion job's host arrays (struct r0hip_recursion_input): the control group and the
+/// preflight as r0hip_recursion_witgen takes them, and the allow-list of its receipt check.
+#[repr(C)]
+pub struct R0HipRecursionInput {
+    pub h_ctrl: *const u32,
+    pub h_wom: *const u32,
+    pub n_wom: usize,
+    pub h_cycles: *const u32,
+    pub n_cycles: usize,
+    pub h_iops: *const u32,
+    pub n_iops: usize,
+    pub h_code_roots: *const u32,
+    pub n_code_roots: usize,
+}
+
+/// One job of the GPU worker (struct r0hip_worker_job): an rv32im prove_core from a preflight
+/// trace (kind 0) or a recursion proof (kind 1). It must not move, and its host arrays must
+/// stay valid, from r0hip_worker_submit until r0hip_worker_wait hands it back.
+#[repr(C)]
+pub struct R0HipWorkerJob {
+    pub kind: u32,
+    pub suite: c_int,
+    pub po2: u32,
+    pub trace: R0HipTraceInput,
+    pub h_bigint: *const R0HipBigIntBack,
+    pub n_bigint: usize,
+    pub recursion: R0HipRecursionInput,
+    pub user: *mut c_void,
+    pub h_seal: *mut u32,
+    pub seal_cap: usize,
+    pub seal_len: usize,
+    pub h_mix_out: *mut u32,
+    pub error: *const c_char,
+    pub verified: c_int,
+    pub verify_ms: f64,
+    pub prove_ms: f64,
+    pub ticket: u64,
+}
+
 #[link(name = "r0hip")]
 unsafe extern "C" {
     // ---- device and memory (cust's role in hal/cuda.rs:235-421) ----
@@ -181,6 +230,8 @@ unsafe extern "C" {
     ) -> *const c_char;
     pub fn r0hip_prefix_products(d_io: *mut u32, count: usize) -> *const c_char;
     pub fn r0hip_fill_uniform(d_out: *mut u32, count: usize, seed: u64) -> *const c_char;
+    /// keyed noise words: the ChaCha20 stream of (h_key, h_nonce) as field elements
+    pub fn r0hip_fill_chacha20(d_out: *mut u32, count: usize, h_key: *const u32, h_nonce: *const u32) -> *const c_char;
 
     // ---- hashing (sppark_poseidon2_*, risc0_zkp_cuda_sha_*, sppark_poseidon254_*) ----
     pub fn r0hip_hash_rows(suite: c_int, d_out: *mut u32, d_matrix: *const u32, rows: usize, cols: usize)
@@ -353,6 +404,24 @@ unsafe extern "C" {
         seal_len: *mut usize,
         h_mix_out: *mut u32,
     ) -> *const c_char;
+    /// the same with the ZK noise from a keyed ChaCha20 stream (h_key NULL: an OS key): the one to ship
+    pub fn r0hip_prove_recursion_keyed(
+        suite: c_int,
+        po2: u32,
+        d_ctrl: *const u32,
+        h_wom: *const u32,
+        n_wom: usize,
+        h_cycles: *const u32,
+        n_cycles: usize,
+        h_iops: *const u32,
+        n_iops: usize,
+        h_key: *const u32,
+        stream_id: u64,
+        h_seal: *mut u32,
+        seal_cap: usize,
+        seal_len: *mut usize,
+        h_mix_out: *mut u32,
+    ) -> *const c_char;
     pub fn r0hip_prove_segments(
         circuit: *const c_char,
         suite: c_int,
@@ -371,6 +440,18 @@ unsafe extern "C" {
         in_flight: u32,
         verify: c_int,
     ) -> *const c_char;
+
+    // ---- the GPU worker: a persistent queue of rv32im and recursion jobs ----
+    pub fn r0hip_worker_create(
+        out: *mut *mut R0HipWorker,
+        max_po2: u32,
+        in_flight: u32,
+        verify: c_int,
+        h_noise_key: *const u32,
+    ) -> *const c_char;
+    pub fn r0hip_worker_submit(w: *mut R0HipWorker, job: *mut R0HipWorkerJob) -> *const c_char;
+    pub fn r0hip_worker_wait(w: *mut R0HipWorker, done: *mut *mut R0HipWorkerJob, timeout_ms: i64) -> *const c_char;
+    pub fn r0hip_worker_destroy(w: *mut R0HipWorker) -> *const c_char;
 
     // ---- verification (host-only) ----
     pub fn r0hip_verify_seal(

@@ -5,6 +5,9 @@
 // malloc'd string (risc0/sys/src/lib.rs:53-75 convention).
 #include "../../include/r0hip.h"
 
+#include <sys/random.h>
+
+#include <cerrno>
 #include <cstdlib>
 #include <algorithm>
 #include <cstring>
@@ -478,6 +481,67 @@ void check_injector(const uint32_t* index, size_t rows, const uint32_t* offsets,
     }
 }
 
+// RecursionProverImpl::prove from the program and its preflight (circuit/recursion/src/prove/
+// mod.rs:160-230). noise(s, out, count, which) fills `count` words of the ZK noise matrix
+// `which` (0 the data group's, 1 the accum group's) on stream s.
+std::vector<uint32_t> prove_recursion(int suite, uint32_t po2, const uint32_t* d_ctrl, const uint32_t* h_wom,
+                                      size_t n_wom, const uint32_t* h_cycles, size_t n_cycles, const uint32_t* h_iops,
+                                      size_t n_iops, const RecursionNoise& noise_fill, std::vector<uint32_t>* mix) {
+  const CircuitDef* c = find_circuit("recursion");
+  R0_REQUIRE(c && d_ctrl, "r0hip_prove_recursion: null argument");
+  R0_REQUIRE(po2 >= 11 && po2 <= 24, "r0hip_prove_recursion: po2 out of range (ZK rows need po2 >= 11)");
+  constexpr size_t kZk = 1024;  // risc0_zkp::ZK_CYCLES (zkp/src/lib.rs:42)
+  const size_t n = size_t(1) << po2;
+  R0_REQUIRE(n_cycles <= n - kZk, "r0hip_prove_recursion: program longer than 2^po2 - ZK_CYCLES rows");
+  const size_t data_cols = c->group_size(2), accum_cols = c->group_size(0);
+  hipStream_t s = stream();
+  stage_reset();
+  // WitnessGenerator::new (circuit/recursion/src/prove/witgen.rs:44-133)
+  DevBuf data(data_cols * n), global(c->output_size), accum(accum_cols * n), noise(std::max(data_cols, accum_cols) * kZk);
+  HIP_OK(hipMemsetD32Async(data.p, 0xFFFFFFFFu, data.words, s));
+  HIP_OK(hipMemsetD32Async(global.p, 0xFFFFFFFFu, global.words, s));
+  recursion_witgen(s, d_ctrl, data.p, global.p, n, h_wom, n_wom, h_cycles, n_cycles, h_iops, n_iops);
+  // ZK noise in the last ZK_CYCLES data rows (witgen.rs:101-116: eltwise_copy_elem_slice
+  // from a data_size x ZK_CYCLES noise matrix), per-cell values of the noise generator
+  noise_fill(s, noise.p, data_cols * kZk, 0);
+  copy_elem_slice(s, data.p, noise.p, data_cols, kZk, 0, kZk, n - kZk, n);
+  eltwise_zeroize(s, data.p, data.words);
+  // WitnessGenerator::accum (witgen.rs:134-177): INVALID plus noise rows, then the
+  // accumulation inside the proof; prove (prove/mod.rs:160-230)
+  HIP_OK(hipMemsetD32Async(accum.p, 0xFFFFFFFFu, accum.words, s));
+  noise_fill(s, noise.p, accum_cols * kZk, 1);
+  copy_elem_slice(s, accum.p, noise.p, accum_cols, kZk, 0, kZk, n - kZk, n);
+  const AccumStep acc{accum.p, n_cycles};
+  return prove_segment(*c, suite, po2, d_ctrl, data.p, nullptr, global.p, false, 0, mix, nullptr, &acc);
+}
+
+// The keyed noise of r0hip_prove_recursion_keyed: ChaCha20 under `key`, the data matrix with
+// nonce {0, lo32(stream_id), hi32(stream_id)}, the accum matrix with {1, lo32, hi32}.
+RecursionNoise keyed_noise(const uint32_t* key, uint64_t stream_id) {
+  return [key, stream_id](hipStream_t s, uint32_t* out, size_t count, uint32_t which) {
+    ChaChaKey k;
+    memcpy(k.key, key, sizeof k.key);
+    k.nonce[0] = which;
+    k.nonce[1] = uint32_t(stream_id);
+    k.nonce[2] = uint32_t(stream_id >> 32);
+    fill_chacha20(s, out, count, k);
+    explicit_bzero(&k, sizeof k);
+  };
+}
+
+void os_random_key(uint32_t key[8]) {
+  auto* p = reinterpret_cast<uint8_t*>(key);
+  for (size_t got = 0; got < 32;) {
+    const ssize_t r = getrandom(p + got, 32 - got, 0);
+    if (r < 0 && errno == EINTR) continue;
+    if (r <= 0) {
+      explicit_bzero(key, 32);
+      throw std::runtime_error(std::string("r0hip: getrandom failed: ") + strerror(errno));
+    }
+    got += size_t(r);
+  }
+}
+
 }  // namespace r0
 
 namespace {
@@ -539,41 +603,44 @@ const char* r0hip_prove_recursion(int suite, uint32_t po2, const uint32_t* d_ctr
                                   uint64_t noise_seed, uint32_t* h_seal, size_t seal_cap, size_t* seal_len,
                                   uint32_t* h_mix_out) {
   return wrap([&] {
-    const CircuitDef* c = find_circuit("recursion");
-    R0_REQUIRE(c && d_ctrl, "r0hip_prove_recursion: null argument");
-    R0_REQUIRE(po2 >= 11 && po2 <= 24, "r0hip_prove_recursion: po2 out of range (ZK rows need po2 >= 11)");
-    constexpr size_t kZk = 1024;  // risc0_zkp::ZK_CYCLES (zkp/src/lib.rs:42)
-    const size_t n = size_t(1) << po2;
-    R0_REQUIRE(n_cycles <= n - kZk, "r0hip_prove_recursion: program longer than 2^po2 - ZK_CYCLES rows");
-    const size_t data_cols = c->group_size(2), accum_cols = c->group_size(0);
-    hipStream_t s = stream();
-    stage_reset();
-    // WitnessGenerator::new (circuit/recursion/src/prove/witgen.rs:44-133)
-    DevBuf data(data_cols * n), global(c->output_size), accum(accum_cols * n), noise(std::max(data_cols, accum_cols) * kZk);
-    HIP_OK(hipMemsetD32Async(data.p, 0xFFFFFFFFu, data.words, s));
-    HIP_OK(hipMemsetD32Async(global.p, 0xFFFFFFFFu, global.words, s));
-    recursion_witgen(s, d_ctrl, data.p, global.p, n, h_wom, n_wom, h_cycles, n_cycles, h_iops, n_iops);
-    // ZK noise in the last ZK_CYCLES data rows (witgen.rs:101-116: eltwise_copy_elem_slice
-    // from a data_size x ZK_CYCLES noise matrix), here per-cell values of r0hip_fill_uniform
-    fill_uniform(s, noise.p, data_cols * kZk, noise_seed);
-    copy_elem_slice(s, data.p, noise.p, data_cols, kZk, 0, kZk, n - kZk, n);
-    eltwise_zeroize(s, data.p, data.words);
-    // WitnessGenerator::accum (witgen.rs:134-177): INVALID plus noise rows, then the
-    // accumulation inside the proof; prove (prove/mod.rs:160-230)
-    HIP_OK(hipMemsetD32Async(accum.p, 0xFFFFFFFFu, accum.words, s));
-    fill_uniform(s, noise.p, accum_cols * kZk, noise_seed + 1);
-    copy_elem_slice(s, accum.p, noise.p, accum_cols, kZk, 0, kZk, n - kZk, n);
     std::vector<uint32_t> mix;
-    const AccumStep acc{accum.p, n_cycles};
-    std::vector<uint32_t> seal =
-        prove_segment(*c, suite, po2, d_ctrl, data.p, nullptr, global.p, false, 0, &mix, nullptr, &acc);
-    if (seal_len) *seal_len = seal.size();
-    if (h_mix_out) memcpy(h_mix_out, mix.data(), mix.size() * 4);
-    if (h_seal) {
-      R0_REQUIRE(seal.size() <= seal_cap, "seal buffer too small");
-      memcpy(h_seal, seal.data(), seal.size() * 4);
-    }
+    auto seal = prove_recursion(suite, po2, d_ctrl, h_wom, n_wom, h_cycles, n_cycles, h_iops, n_iops,
+                                [noise_seed](hipStream_t s, uint32_t* out, size_t count, uint32_t which) {
+                                  fill_uniform(s, out, count, noise_seed + which);
+                                },
+                                &mix);
+    seal_out(seal, mix, h_seal, seal_cap, seal_len, h_mix_out);
   });
+}
+
+const char* r0hip_prove_recursion_keyed(int suite, uint32_t po2, const uint32_t* d_ctrl, const uint32_t* h_wom,
+                                        size_t n_wom, const uint32_t* h_cycles, size_t n_cycles,
+                                        const uint32_t* h_iops, size_t n_iops, const uint32_t* h_key,
+                                        uint64_t stream_id, uint32_t* h_seal, size_t seal_cap, size_t* seal_len,
+                                        uint32_t* h_mix_out) {
+  uint32_t key[8];
+  const char* err = wrap([&] {
+    if (h_key) memcpy(key, h_key, sizeof key);
+    else os_random_key(key);
+    std::vector<uint32_t> mix;
+    auto seal = prove_recursion(suite, po2, d_ctrl, h_wom, n_wom, h_cycles, n_cycles, h_iops, n_iops,
+                                keyed_noise(key, stream_id), &mix);
+    seal_out(seal, mix, h_seal, seal_cap, seal_len, h_mix_out);
+  });
+  explicit_bzero(key, sizeof key);
+  return err;
+}
+
+const char* r0hip_fill_chacha20(uint32_t* d_out, size_t count, const uint32_t* h_key, const uint32_t* h_nonce) {
+  ChaChaKey k;
+  const char* err = wrap([&] {
+    R0_REQUIRE((d_out || !count) && h_key && h_nonce, "r0hip_fill_chacha20: null argument");
+    memcpy(k.key, h_key, sizeof k.key);
+    memcpy(k.nonce, h_nonce, sizeof k.nonce);
+    fill_chacha20(stream(), d_out, count, k);
+  });
+  explicit_bzero(&k, sizeof k);
+  return err;
 }
 
 const char* r0hip_fill_uniform(uint32_t* d_out, size_t count, uint64_t seed) {

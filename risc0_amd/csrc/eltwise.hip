@@ -45,6 +45,57 @@ __global__ void fill_uniform_kernel(uint32_t* o, uint64_t n, uint64_t seed) {
     o[i] = uint32_t(z % kP);
   }
 }
+// Keyed noise words: the ChaCha20 keystream of RFC 8439 §2.3 (20 rounds, 32-bit block counter
+// from 0), one lane per 64-byte block. Element i is the 128-bit little-endian integer of
+// keystream words 4i..4i+3 reduced mod p, so block b holds elements 4b..4b+3 and the words do
+// not depend on the launch shape. Key and nonce arrive as kernel arguments.
+#define R0_CHACHA_QR(a, b, c, d)                   \
+  a += b, d = __builtin_rotateleft32(d ^ a, 16);   \
+  c += d, b = __builtin_rotateleft32(b ^ c, 12);   \
+  a += b, d = __builtin_rotateleft32(d ^ a, 8);    \
+  c += d, b = __builtin_rotateleft32(b ^ c, 7)
+__global__ __launch_bounds__(kThreads) void fill_chacha20_kernel(uint32_t* o, uint64_t n, ChaChaKey key) {
+  const uint64_t blocks = (n + 3) / 4;
+  const bool aligned = (reinterpret_cast<uintptr_t>(o) & 15) == 0;
+  for (uint64_t b = uint64_t(blockIdx.x) * kThreads + threadIdx.x; b < blocks; b += uint64_t(gridDim.x) * kThreads) {
+    uint32_t in[16] = {0x61707865u, 0x3320646eu, 0x79622d32u, 0x6b206574u,
+                       key.key[0],  key.key[1],  key.key[2],  key.key[3],
+                       key.key[4],  key.key[5],  key.key[6],  key.key[7],
+                       uint32_t(b), key.nonce[0], key.nonce[1], key.nonce[2]};
+    uint32_t x[16];
+#pragma unroll
+    for (int k = 0; k < 16; k++) x[k] = in[k];
+#pragma unroll
+    for (int r = 0; r < 10; r++) {
+      R0_CHACHA_QR(x[0], x[4], x[8], x[12]);
+      R0_CHACHA_QR(x[1], x[5], x[9], x[13]);
+      R0_CHACHA_QR(x[2], x[6], x[10], x[14]);
+      R0_CHACHA_QR(x[3], x[7], x[11], x[15]);
+      R0_CHACHA_QR(x[0], x[5], x[10], x[15]);
+      R0_CHACHA_QR(x[1], x[6], x[11], x[12]);
+      R0_CHACHA_QR(x[2], x[7], x[8], x[13]);
+      R0_CHACHA_QR(x[3], x[4], x[9], x[14]);
+    }
+    uint32_t e[4];
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+      // (w3 2^96 + w2 2^64 + w1 2^32 + w0) mod p, most significant word first
+      uint64_t v = (x[4 * j + 3] + in[4 * j + 3]) % kP;
+#pragma unroll
+      for (int k = 2; k >= 0; k--) v = ((v << 32) | (x[4 * j + k] + in[4 * j + k])) % kP;
+      e[j] = uint32_t(v);
+    }
+    const uint64_t i = 4 * b;
+    if (aligned && i + 4 <= n) {
+      *reinterpret_cast<uint4*>(o + i) = make_uint4(e[0], e[1], e[2], e[3]);
+    } else {
+#pragma unroll
+      for (int j = 0; j < 4; j++)
+        if (i + j < n) o[i + j] = e[j];
+    }
+  }
+}
+#undef R0_CHACHA_QR
 // cpu.rs:475-500: out[k*count + idx] = (sum_i in[i*count + idx])[k]
 __global__ void sum_extelem_kernel(uint32_t* out, const uint32_t* in, uint64_t count, uint32_t to_add) {
   uint64_t idx = uint64_t(blockIdx.x) * kThreads + threadIdx.x;
@@ -475,6 +526,13 @@ void eltwise_zeroize(hipStream_t s, uint32_t* io, size_t n) {
 void fill_uniform(hipStream_t s, uint32_t* out, size_t n, uint64_t seed) {
   if (!n) return;
   hipLaunchKernelGGL(fill_uniform_kernel, dim3(grid_stride(n, kThreads)), dim3(kThreads), 0, s, out, uint64_t(n), seed);
+  HIP_OK(hipGetLastError());
+}
+void fill_chacha20(hipStream_t s, uint32_t* out, size_t n, const ChaChaKey& key) {
+  if (!n) return;
+  R0_REQUIRE(n <= (size_t(1) << 34), "fill_chacha20: more than 2^34 elements (the block counter is 32 bits)");
+  hipLaunchKernelGGL(fill_chacha20_kernel, dim3(grid_stride((n + 3) / 4, kThreads)), dim3(kThreads), 0, s, out,
+                     uint64_t(n), key);
   HIP_OK(hipGetLastError());
 }
 void eltwise_sum_extelem(hipStream_t s, uint32_t* out, const uint32_t* in, size_t count, size_t to_add) {

@@ -11,6 +11,10 @@
 // (runtime.cpp gives every host thread its own stream, pool and staging), write the
 // seal, and hand the set back. in_flight + 1 sets circulate, so an upload is always
 // running ahead while the GPU proves. Each job reports its own error.
+//
+// r0hip_prove_segments and r0hip_prove_trace_segments take every job up front and return when
+// all are proved; the worker (r0hip_worker_*, below) keeps the trace pipeline's threads and sets
+// alive between jobs and takes rv32im jobs of any po2 and recursion jobs as they arrive.
 #include <condition_variable>
 #include <cstdlib>
 #include <cstring>
@@ -157,6 +161,57 @@ struct TraceSet {
   }
 };
 
+constexpr size_t kCycleWords = 9, kTxnWords = 5, kGlobalWords = 90;  // RawPreflightCycle 36 B, txn 20 B
+
+// The host checks of one trace job (n = 2^po2); throws the job's error.
+void check_trace_input(const r0hip_trace_input& t, const r0hip_bigint_back* h_bigint, size_t n_bigint, size_t n) {
+  const r0hip_raw_preflight_trace& pf = t.preflight;
+  R0_REQUIRE(t.h_global && t.h_inj_index && pf.cycles, "trace job: null argument");
+  R0_REQUIRE(t.inj_rows <= n, "trace job: injector longer than the segment");
+  R0_REQUIRE((pf.txns_len == 0 || pf.txns) && (pf.bigint_bytes_len == 0 || pf.bigint_bytes),
+             "trace job: null trace array with a nonzero count");
+  R0_REQUIRE(n_bigint == 0 || h_bigint, "trace job: h_bigint is NULL with n_bigint > 0");
+  check_injector(t.h_inj_index, t.inj_rows, t.h_inj_offsets, t.h_inj_values, size_t(211) * n, n);
+}
+
+// The uploader's copies of one checked trace job: the trace, the injector and the global vector
+// into set b on the uploader's stream, then b.ev recorded. The set's buffers hold the job (the
+// callers size them).
+void upload_trace(TraceSet& b, const r0hip_trace_input& t, size_t n) {
+  const r0hip_raw_preflight_trace& pf = t.preflight;
+  const size_t n_inj = t.h_inj_index[t.inj_rows];
+  stage_reset();  // the previous job's staged copies have landed: the arena is free
+  upload_async(b.glob.p, t.h_global, kGlobalWords * 4);
+  upload_async(b.index.p, t.h_inj_index, (t.inj_rows + 1) * 4);
+  upload_async(b.offsets.p, t.h_inj_offsets, n_inj * 4);
+  upload_async(b.values.p, t.h_inj_values, n_inj * 4);
+  upload_async(b.cycles.p, pf.cycles, n * kCycleWords * 4);
+  upload_async(b.txns.p, pf.txns, size_t(pf.txns_len) * kTxnWords * 4);
+  upload_async(b.bigint.p, pf.bigint_bytes, pf.bigint_bytes_len);
+  HIP_OK(hipEventRecord(b.ev, stream()));
+}
+
+// The prover's part: prove_trace from the set's device copies. Its stream waits for the set's
+// upload just before the first read of an input; *error (written by the uploader under b.mu)
+// is the job's staging error, rethrown here.
+std::vector<uint32_t> prove_staged_trace(TraceSet& b, int suite, uint32_t po2, const r0hip_trace_input& tr,
+                                         const r0hip_bigint_back* h_bigint, size_t n_bigint,
+                                         const char* const* error, std::vector<uint32_t>* mix) {
+  r0hip_raw_preflight_trace pf = tr.preflight;  // the set's device copies
+  pf.cycles = b.cycles.p;
+  pf.txns = pf.txns_len ? b.txns.p : nullptr;
+  pf.bigint_bytes = pf.bigint_bytes_len ? reinterpret_cast<const uint8_t*>(b.bigint.p) : nullptr;
+  return prove_trace(suite, po2, tr.mode, b.glob.p, b.index.p, tr.inj_rows, b.offsets.p, b.values.p, &pf, h_bigint,
+                     n_bigint, true, mix, [&](hipStream_t st) {
+                       b.wait_landed();
+                       {
+                         std::lock_guard<std::mutex> lk(b.mu);
+                         if (*error) throw std::runtime_error(*error);
+                       }
+                       HIP_OK(hipStreamWaitEvent(st, b.ev, 0));
+                     });
+}
+
 // Trace jobs: the uploader copies job i's trace into a free trace set and hands the set to a
 // prover at once; the prover allocates its witness groups and queues their fill (which reads no
 // input), then waits on the host until the uploader has queued the set's copies and makes its
@@ -168,9 +223,7 @@ struct TraceSet {
 // prove_segment_core verifies a receipt before it returns it (zkvm/src/host/server/prove/
 // prover_impl.rs:262-280); a seal that fails fails its job.
 const char* prove_trace_jobs(int suite, uint32_t po2, r0hip_trace_job* jobs, size_t njobs, size_t k, bool verify) {
-  constexpr size_t kCycleWords = 9, kTxnWords = 5, kGlobalWords = 90;  // RawPreflightCycle 36 B, txn 20 B
   const size_t n = size_t(1) << po2;
-  const size_t data_words = size_t(211) * n;
   size_t cap_inj = 1, cap_txn = 1, cap_big = 4;
   for (size_t i = 0; i < njobs; i++) {
     const r0hip_trace_input* t = &jobs[i].trace;
@@ -212,24 +265,8 @@ const char* prove_trace_jobs(int suite, uint32_t po2, r0hip_trace_job* jobs, siz
       ready_q.put(s);  // the prover fills its groups while the trace uploads
       try {
         ensure_init();
-        const r0hip_trace_input& t = jobs[i].trace;
-        const r0hip_raw_preflight_trace& pf = t.preflight;
-        R0_REQUIRE(t.h_global && t.h_inj_index && pf.cycles, "trace job: null argument");
-        R0_REQUIRE(t.inj_rows <= n, "trace job: injector longer than the segment");
-        R0_REQUIRE((pf.txns_len == 0 || pf.txns) && (pf.bigint_bytes_len == 0 || pf.bigint_bytes),
-                   "trace job: null trace array with a nonzero count");
-        R0_REQUIRE(jobs[i].n_bigint == 0 || jobs[i].h_bigint, "trace job: h_bigint is NULL with n_bigint > 0");
-        check_injector(t.h_inj_index, t.inj_rows, t.h_inj_offsets, t.h_inj_values, data_words, n);
-        const size_t n_inj = t.h_inj_index[t.inj_rows];
-        stage_reset();  // the previous job's staged copies have landed: the arena is free
-        upload_async(b.glob.p, t.h_global, kGlobalWords * 4);
-        upload_async(b.index.p, t.h_inj_index, (t.inj_rows + 1) * 4);
-        upload_async(b.offsets.p, t.h_inj_offsets, n_inj * 4);
-        upload_async(b.values.p, t.h_inj_values, n_inj * 4);
-        upload_async(b.cycles.p, pf.cycles, n * kCycleWords * 4);
-        upload_async(b.txns.p, pf.txns, size_t(pf.txns_len) * kTxnWords * 4);
-        upload_async(b.bigint.p, pf.bigint_bytes, pf.bigint_bytes_len);
-        HIP_OK(hipEventRecord(b.ev, stream()));
+        check_trace_input(jobs[i].trace, jobs[i].h_bigint, jobs[i].n_bigint, n);
+        upload_trace(b, jobs[i].trace, n);
       } catch (const std::exception& e) {
         {
           std::lock_guard<std::mutex> lk(b.mu);
@@ -299,21 +336,8 @@ const char* prove_trace_jobs(int suite, uint32_t po2, r0hip_trace_job* jobs, siz
       const auto t0 = std::chrono::steady_clock::now();
       try {
         ensure_init();
-        r0hip_raw_preflight_trace pf = tr.preflight;  // the set's device copies
-        pf.cycles = b.cycles.p;
-        pf.txns = pf.txns_len ? b.txns.p : nullptr;
-        pf.bigint_bytes = pf.bigint_bytes_len ? reinterpret_cast<const uint8_t*>(b.bigint.p) : nullptr;
         std::vector<uint32_t> mix;
-        std::vector<uint32_t> seal = prove_trace(
-            suite, po2, tr.mode, b.glob.p, b.index.p, tr.inj_rows, b.offsets.p, b.values.p, &pf, j.h_bigint,
-            j.n_bigint, true, &mix, [&](hipStream_t st) {
-              b.wait_landed();
-              {
-                std::lock_guard<std::mutex> lk(b.mu);
-                if (j.error) throw std::runtime_error(j.error);
-              }
-              HIP_OK(hipStreamWaitEvent(st, b.ev, 0));
-            });
+        std::vector<uint32_t> seal = prove_staged_trace(b, suite, po2, tr, j.h_bigint, j.n_bigint, &j.error, &mix);
         HIP_OK(hipStreamSynchronize(stream()));
         j.prove_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
         j.seal_len = seal.size();
@@ -345,6 +369,236 @@ const char* prove_trace_jobs(int suite, uint32_t po2, r0hip_trace_job* jobs, siz
     if (jobs[i].error) return dup_msg((std::string("segment ") + std::to_string(i) + ": " + jobs[i].error).c_str());
   return nullptr;
 }
+
+
+// ---- the worker: a persistent queue of mixed jobs (r0hip_worker_*) ----------------------------
+// The threads and sets of prove_trace_jobs kept alive between jobs: the uploader takes jobs from
+// a FIFO in ticket order, stages each into a free set and hands the set to a prover at once; a
+// prover's stream waits on the set's event before the first read of a staged input; finished
+// seals go to the verifier thread (or straight to the finished list) and r0hip_worker_wait
+// hands them out in completion order. The trace buffers of a set are sized for max_po2; the
+// injector, transaction, BigInt and control-group buffers grow on the uploader thread while the
+// set is free, before the set is handed to a prover (which reads their pointers then).
+struct WorkerSet : TraceSet {
+  DevBuf ctrl;  // recursion jobs: the control group (allocated at the set's first one)
+  r0hip_worker_job* wjob = nullptr;
+  size_t cap_inj = 0, cap_txn = 0, cap_big = 0;  // entries, records, bytes
+};
+
+struct WorkerImpl {
+  uint32_t max_po2 = 0;
+  size_t k = 0;
+  bool verify = false;
+  uint32_t key[8] = {};
+  std::vector<WorkerSet> sets;
+  Queue free_q, ready_q;
+  std::mutex mu;  // fifo, finished, next_ticket, outstanding, stopping
+  std::condition_variable cv_in, cv_done;
+  std::deque<r0hip_worker_job*> fifo, finished;
+  uint64_t next_ticket = 0;
+  size_t outstanding = 0;
+  bool stopping = false;
+  std::mutex vmu;
+  std::condition_variable vcv;
+  std::deque<std::pair<r0hip_worker_job*, std::vector<uint32_t>>> vq;
+  std::thread uploader, verifier;
+  std::vector<std::thread> provers;
+
+  void finish(r0hip_worker_job* j) {
+    {
+      std::lock_guard<std::mutex> lk(mu);
+      finished.push_back(j);
+    }
+    cv_done.notify_all();
+  }
+  void to_verifier(r0hip_worker_job* j, std::vector<uint32_t> seal) {
+    {
+      std::lock_guard<std::mutex> lk(vmu);
+      vq.emplace_back(j, std::move(seal));
+    }
+    vcv.notify_one();
+  }
+
+  // the set is free (its last prover drained its stream): make its buffers hold job j
+  void grow(WorkerSet& b, const r0hip_worker_job& j) {
+    const size_t n = size_t(1) << j.po2;
+    if (j.kind == R0HIP_JOB_RECURSION) {
+      if (b.ctrl.words < 23 * n) b.ctrl = DevBuf(23 * n);
+      return;
+    }
+    const r0hip_trace_input& t = j.trace;
+    // an index that names more entries than the data group has words is refused by run_uploader
+    const size_t n_inj = t.inj_rows <= n ? t.h_inj_index[t.inj_rows] : 0;
+    if (n_inj > b.cap_inj && n_inj <= 211 * n) {
+      b.offsets = DevBuf(n_inj);
+      b.values = DevBuf(n_inj);
+      b.cap_inj = n_inj;
+    }
+    if (t.preflight.txns_len > b.cap_txn) {
+      b.txns = DevBuf(size_t(t.preflight.txns_len) * kTxnWords);
+      b.cap_txn = t.preflight.txns_len;
+    }
+    if (t.preflight.bigint_bytes_len > b.cap_big) {
+      b.bigint = DevBuf((size_t(t.preflight.bigint_bytes_len) + 3) / 4);
+      b.cap_big = t.preflight.bigint_bytes_len;
+    }
+  }
+
+  void run_uploader() {
+    for (;;) {
+      r0hip_worker_job* j;
+      {
+        std::unique_lock<std::mutex> lk(mu);
+        cv_in.wait(lk, [&] { return !fifo.empty() || stopping; });
+        if (fifo.empty()) break;
+        j = fifo.front();
+        fifo.pop_front();
+      }
+      const long s = free_q.get();
+      WorkerSet& b = sets[s];
+      auto fail = [&](const char* what) {
+        {
+          std::lock_guard<std::mutex> lk(b.mu);
+          if (!j->error) j->error = dup_msg(what);
+        }
+        drain_after_error();
+      };
+      bool ok = true;
+      {
+        std::lock_guard<std::mutex> lk(b.mu);
+        b.wjob = j;
+        b.landed = false;
+      }
+      try {
+        ensure_init();
+        grow(b, *j);
+      } catch (const std::exception& e) {
+        fail(e.what());
+        ok = false;
+      }
+      ready_q.put(s);  // the prover fills its groups while the inputs upload
+      if (ok) try {
+          const size_t n = size_t(1) << j->po2;
+          if (j->kind == R0HIP_JOB_RECURSION) {
+            stage_reset();
+            upload_async(b.ctrl.p, j->recursion.h_ctrl, 23 * n * 4);
+            HIP_OK(hipEventRecord(b.ev, stream()));
+          } else {
+            check_trace_input(j->trace, j->h_bigint, j->n_bigint, n);
+            R0_REQUIRE(j->trace.h_inj_index[j->trace.inj_rows] <= b.cap_inj,
+                       "trace job: the injector has more entries than the data group has words");
+            upload_trace(b, j->trace, n);
+          }
+        } catch (const std::exception& e) {
+          fail(e.what());
+        }
+      b.mark();
+    }
+    // every copy done before the threads end
+    drain_after_error();
+    for (size_t t = 0; t < k; t++) ready_q.put(-1);
+  }
+
+  void run_prover() {
+    for (;;) {
+      const long s = ready_q.get();
+      if (s < 0) return;
+      WorkerSet& b = sets[s];
+      r0hip_worker_job* j;
+      {
+        std::lock_guard<std::mutex> lk(b.mu);
+        j = b.wjob;
+      }
+      const auto t0 = std::chrono::steady_clock::now();
+      std::vector<uint32_t> seal;
+      bool ok = false;
+      try {
+        ensure_init();
+        std::vector<uint32_t> mix;
+        if (j->kind == R0HIP_JOB_RECURSION) {
+          b.wait_landed();
+          {
+            std::lock_guard<std::mutex> lk(b.mu);
+            if (j->error) throw std::runtime_error(j->error);
+          }
+          HIP_OK(hipStreamWaitEvent(stream(), b.ev, 0));
+          const r0hip_recursion_input& in = j->recursion;
+          seal = prove_recursion(j->suite, j->po2, b.ctrl.p, in.h_wom, in.n_wom, in.h_cycles, in.n_cycles, in.h_iops,
+                                 in.n_iops, keyed_noise(key, j->ticket), &mix);
+        } else {
+          seal = prove_staged_trace(b, j->suite, j->po2, j->trace, j->h_bigint, j->n_bigint, &j->error, &mix);
+        }
+        HIP_OK(hipStreamSynchronize(stream()));
+        j->prove_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        j->seal_len = seal.size();
+        if (j->h_mix_out) memcpy(j->h_mix_out, mix.data(), mix.size() * 4);
+        R0_REQUIRE(!j->h_seal || seal.size() <= j->seal_cap, "seal buffer too small");
+        if (j->h_seal) memcpy(j->h_seal, seal.data(), seal.size() * 4);
+        ok = true;
+      } catch (const std::exception& e) {
+        {
+          std::lock_guard<std::mutex> lk(b.mu);
+          if (!j->error) j->error = dup_msg(e.what());
+        }
+        drain_after_error();  // kernels queued before the throw may still read this set
+      }
+      b.wait_landed();  // the uploader is done with this job before the set is refilled
+      free_q.put(s);
+      if (ok && verify) to_verifier(j, std::move(seal));
+      else finish(j);
+    }
+  }
+
+  void run_verifier() {
+    for (;;) {
+      std::pair<r0hip_worker_job*, std::vector<uint32_t>> item;
+      {
+        std::unique_lock<std::mutex> lk(vmu);
+        vcv.wait(lk, [&] { return !vq.empty(); });
+        item = std::move(vq.front());
+        vq.pop_front();
+      }
+      r0hip_worker_job* j = item.first;
+      if (!j) return;
+      const bool rec = j->kind == R0HIP_JOB_RECURSION;
+      const auto t0 = std::chrono::steady_clock::now();
+      uint32_t got = 0;
+      const char* err = r0hip_verify_seal(rec ? "recursion" : "rv32im", j->suite, item.second.data(),
+                                          item.second.size(), rec ? j->recursion.h_code_roots : nullptr,
+                                          rec ? j->recursion.n_code_roots : 0, nullptr, &got);
+      j->verify_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+      if (!err && got != j->po2) err = dup_msg("the seal is of another segment size");
+      if (err) {
+        j->error = dup_msg((std::string("receipt verification failed: ") + err).c_str());
+        free(const_cast<char*>(err));
+      } else {
+        j->verified = 1;
+      }
+      finish(j);
+    }
+  }
+
+  // runs everything submitted to completion, joins the threads, frees the sets
+  void shutdown() {
+    {
+      std::lock_guard<std::mutex> lk(mu);
+      stopping = true;
+    }
+    cv_in.notify_all();
+    if (uploader.joinable()) uploader.join();
+    else
+      for (size_t t = 0; t < provers.size(); t++) ready_q.put(-1);  // create failed before the uploader
+    for (auto& t : provers) t.join();
+    if (verifier.joinable()) {
+      to_verifier(nullptr, {});
+      verifier.join();
+    }
+    for (auto& b : sets)
+      if (b.ev) (void)hipEventDestroy(b.ev);
+    sets.clear();
+    explicit_bzero(key, sizeof key);
+  }
+};
 
 }  // namespace
 }  // namespace r0
@@ -546,6 +800,144 @@ extern "C" const char* r0hip_prove_trace_segments(int suite, uint32_t po2, r0hip
     err = dup_msg("r0hip: unknown error");
   }
   // the trace sets are freed; the calling thread (one of the provers) keeps no device memory
+  drain_after_error();
+  release_thread_memory();
+  return err;
+}
+
+// ---- the worker's C ABI ----
+struct r0hip_worker {
+  WorkerImpl impl;
+};
+
+namespace {
+template <typename F>
+const char* guarded(F f) {
+  try {
+    f();
+  } catch (const std::exception& e) {
+    return dup_msg(e.what());
+  } catch (...) {
+    return dup_msg("r0hip: unknown error");
+  }
+  return nullptr;
+}
+}  // namespace
+
+extern "C" const char* r0hip_worker_create(r0hip_worker** out, uint32_t max_po2, uint32_t in_flight, int verify,
+                                           const uint32_t* h_noise_key) {
+  r0hip_worker* w = nullptr;
+  const char* err = guarded([&] {
+    R0_REQUIRE(out, "r0hip_worker_create: out is NULL");
+    *out = nullptr;
+    R0_REQUIRE(max_po2 >= 2 && max_po2 <= 24, "r0hip_worker_create: max_po2 out of range");
+    R0_REQUIRE(in_flight <= 8, "r0hip_worker_create: in_flight above 8");
+    ensure_init();
+    w = new r0hip_worker;
+    WorkerImpl& m = w->impl;
+    m.max_po2 = max_po2;
+    m.k = in_flight ? in_flight : 2;
+    m.verify = verify != 0;
+    if (h_noise_key) memcpy(m.key, h_noise_key, sizeof m.key);
+    else os_random_key(m.key);
+    const size_t n = size_t(1) << max_po2;
+    m.sets = std::vector<WorkerSet>(m.k + 1);
+    for (auto& s : m.sets) {
+      s.glob = DevBuf(kGlobalWords);
+      s.index = DevBuf(n + 1);
+      s.cycles = DevBuf(n * kCycleWords);
+      s.offsets = DevBuf(1);
+      s.values = DevBuf(1);
+      s.txns = DevBuf(kTxnWords);
+      s.bigint = DevBuf(1);
+      s.cap_inj = 1, s.cap_txn = 1, s.cap_big = 4;
+      HIP_OK(hipEventCreateWithFlags(&s.ev, hipEventDisableTiming));
+    }
+    HIP_OK(hipDeviceSynchronize());  // allocations complete before other streams use them
+    for (size_t s = 0; s < m.sets.size(); s++) m.free_q.put(long(s));
+    for (size_t t = 0; t < m.k; t++) m.provers.emplace_back([&m] { m.run_prover(); });
+    if (m.verify) m.verifier = std::thread([&m] { m.run_verifier(); });
+    m.uploader = std::thread([&m] { m.run_uploader(); });
+    *out = w;
+  });
+  if (err && w) {
+    w->impl.shutdown();
+    delete w;
+  }
+  if (err) {
+    drain_after_error();
+    release_thread_memory();
+  }
+  return err;
+}
+
+extern "C" const char* r0hip_worker_submit(r0hip_worker* w, r0hip_worker_job* job) {
+  return guarded([&] {
+    R0_REQUIRE(w && job, "r0hip_worker_submit: null argument");
+    WorkerImpl& m = w->impl;
+    R0_REQUIRE(job->kind == R0HIP_JOB_RV32IM_TRACE || job->kind == R0HIP_JOB_RECURSION,
+               "r0hip_worker_submit: unknown job kind");
+    R0_REQUIRE(job->suite >= 0 && job->suite <= 2, "r0hip_worker_submit: unknown hash suite");
+    R0_REQUIRE(job->po2 <= m.max_po2, "r0hip_worker_submit: po2 " + std::to_string(job->po2) +
+                                          " above the worker's max_po2 " + std::to_string(m.max_po2));
+    R0_REQUIRE(!job->seal_cap || job->h_seal, "r0hip_worker_submit: h_seal is NULL with seal_cap > 0");
+    if (job->kind == R0HIP_JOB_RECURSION) {
+      const r0hip_recursion_input& in = job->recursion;
+      R0_REQUIRE(job->po2 >= 11, "r0hip_worker_submit: recursion po2 below 11 (the ZK rows need po2 >= 11)");
+      R0_REQUIRE(in.n_cycles <= (size_t(1) << job->po2) - 1024,
+                 "r0hip_worker_submit: program longer than 2^po2 - ZK_CYCLES rows");
+      R0_REQUIRE(in.h_ctrl && (in.h_wom || !in.n_wom) && (in.h_cycles || !in.n_cycles) && (in.h_iops || !in.n_iops) &&
+                     (in.h_code_roots || !in.n_code_roots),
+                 "r0hip_worker_submit: recursion job: null argument");
+    } else {
+      const r0hip_trace_input& t = job->trace;
+      R0_REQUIRE(job->po2 >= 2, "r0hip_worker_submit: po2 out of range");
+      R0_REQUIRE(t.h_global && t.h_inj_index && t.preflight.cycles, "r0hip_worker_submit: trace job: null argument");
+      R0_REQUIRE((t.preflight.txns_len == 0 || t.preflight.txns) &&
+                     (t.preflight.bigint_bytes_len == 0 || t.preflight.bigint_bytes),
+                 "r0hip_worker_submit: trace job: null trace array with a nonzero count");
+      R0_REQUIRE(job->n_bigint == 0 || job->h_bigint, "r0hip_worker_submit: h_bigint is NULL with n_bigint > 0");
+    }
+    job->error = nullptr;
+    job->seal_len = 0;
+    job->verified = 0;
+    job->verify_ms = 0;
+    job->prove_ms = 0;
+    {
+      std::lock_guard<std::mutex> lk(m.mu);
+      R0_REQUIRE(!m.stopping, "r0hip_worker_submit: the worker is shutting down");
+      job->ticket = m.next_ticket++;
+      m.outstanding++;
+      m.fifo.push_back(job);
+    }
+    m.cv_in.notify_one();
+  });
+}
+
+extern "C" const char* r0hip_worker_wait(r0hip_worker* w, r0hip_worker_job** done, int64_t timeout_ms) {
+  return guarded([&] {
+    R0_REQUIRE(w && done, "r0hip_worker_wait: null argument");
+    *done = nullptr;
+    WorkerImpl& m = w->impl;
+    std::unique_lock<std::mutex> lk(m.mu);
+    if (m.outstanding == 0) return;
+    auto ready = [&] { return !m.finished.empty(); };
+    if (timeout_ms < 0) m.cv_done.wait(lk, ready);
+    else if (!m.cv_done.wait_for(lk, std::chrono::milliseconds(std::min<int64_t>(timeout_ms, int64_t(1) << 40)), ready))
+      return;
+    *done = m.finished.front();
+    m.finished.pop_front();
+    m.outstanding--;
+  });
+}
+
+extern "C" const char* r0hip_worker_destroy(r0hip_worker* w) {
+  const char* err = guarded([&] {
+    R0_REQUIRE(w, "r0hip_worker_destroy: null argument");
+    w->impl.shutdown();
+    delete w;
+  });
+  // the sets are freed; the calling thread keeps no device memory
   drain_after_error();
   release_thread_memory();
   return err;

@@ -248,6 +248,24 @@ void eltwise_add(hipStream_t s, uint32_t* out, const uint32_t* a, const uint32_t
 void eltwise_copy(hipStream_t s, uint32_t* out, const uint32_t* in, size_t n);
 void eltwise_zeroize(hipStream_t s, uint32_t* io, size_t n);
 void fill_uniform(hipStream_t s, uint32_t* out, size_t n, uint64_t seed);
+// A ChaCha20 key and nonce as the RFC 8439 state words (little-endian), passed to the kernel by
+// value. fill_chacha20: out[i] = keystream words 4i..4i+3 (block counter from 0) as a 128-bit
+// little-endian integer mod p, n <= 2^34.
+struct ChaChaKey {
+  uint32_t key[8];
+  uint32_t nonce[3];
+};
+void fill_chacha20(hipStream_t s, uint32_t* out, size_t n, const ChaChaKey& key);
+// 32 bytes from getrandom(2); throws when the OS gives none (there is no weaker source)
+void os_random_key(uint32_t key[8]);
+// The ZK noise of a recursion proof (api.cpp): fill `count` words of noise matrix `which` (0 the
+// data group's, 1 the accum group's) on stream s. keyed_noise: the ChaCha20 stream under `key`
+// (8 words, read at each fill) with nonce {which, lo32(stream_id), hi32(stream_id)}.
+using RecursionNoise = std::function<void(hipStream_t s, uint32_t* out, size_t count, uint32_t which)>;
+RecursionNoise keyed_noise(const uint32_t* key, uint64_t stream_id);
+std::vector<uint32_t> prove_recursion(int suite, uint32_t po2, const uint32_t* d_ctrl, const uint32_t* h_wom,
+                                      size_t n_wom, const uint32_t* h_cycles, size_t n_cycles, const uint32_t* h_iops,
+                                      size_t n_iops, const RecursionNoise& noise_fill, std::vector<uint32_t>* mix);
 void rv32im_accum_finalize(hipStream_t s, uint32_t* accum, size_t rows, size_t cols, size_t split, size_t last);
 void rv32im_accum(hipStream_t s, const uint32_t* data, uint32_t* accum, const uint32_t* global,
                   const uint32_t* mix, size_t rows, size_t cols, size_t last);

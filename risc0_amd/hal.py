@@ -56,6 +56,7 @@ def _declare(L):
         "r0hip_memcpy_d2h_start": [vp, vp, sz, C.POINTER(vp)],
         "r0hip_copy_finish": [vp, C.c_int, C.POINTER(C.c_int)],
         "r0hip_fill_uniform": [vp, sz, C.c_uint64],
+        "r0hip_fill_chacha20": [vp, sz, u32p, u32p],
         "r0hip_rv32im_accum_finalize": [vp, sz, sz, sz],
         "r0hip_rv32im_accum": [vp, vp, vp, vp, sz, sz, sz],
         "r0hip_recursion_accum": [vp, vp, vp, vp, vp, sz, sz],
@@ -102,6 +103,12 @@ def _declare(L):
                                       sz, C.POINTER(sz), u32p],
         "r0hip_prove_recursion": [C.c_int, C.c_uint32, vp, u32p, sz, u32p, sz, u32p, sz, C.c_uint64, u32p, sz,
                                   C.POINTER(sz), u32p],
+        "r0hip_prove_recursion_keyed": [C.c_int, C.c_uint32, vp, u32p, sz, u32p, sz, u32p, sz, u32p, C.c_uint64, u32p,
+                                        sz, C.POINTER(sz), u32p],
+        "r0hip_worker_create": [C.POINTER(vp), C.c_uint32, C.c_uint32, C.c_int, u32p],
+        "r0hip_worker_submit": [vp, vp],
+        "r0hip_worker_wait": [vp, C.POINTER(vp), C.c_int64],
+        "r0hip_worker_destroy": [vp],
         "r0hip_rv32im_bigint_accum_inject": [vp, sz, u32p, vp, sz],
         "r0hip_last_profile": [C.c_char_p, sz],
         "r0hip_set_kernel_timing": [C.c_int],
@@ -493,6 +500,51 @@ def prove_recursion(hal, po2, ctrl, wom, cycles, iops, noise_seed, seal_cap=1 <<
     return seal[: n.value].copy(), mix
 
 
+def _key_words(key):
+    """a ChaCha20 key as 8 little-endian words, from 32 bytes or 8 words (None -> NULL: an OS key)"""
+    if key is None:
+        return None, None
+    k = np.frombuffer(bytes(key), dtype="<u4") if isinstance(key, (bytes, bytearray)) else \
+        np.ascontiguousarray(key, dtype=np.uint32).reshape(-1)
+    if k.size != 8:
+        raise R0HipError("a ChaCha20 key is 8 words (32 bytes)")
+    k = np.ascontiguousarray(k, dtype=np.uint32)
+    return k, k.ctypes.data_as(u32p)
+
+
+def fill_chacha20(buf, key, nonce, count=None, offset=0):
+    """r0hip_fill_chacha20: words [offset, offset + count) of `buf` <- elements 0..count-1 of the
+    ChaCha20 stream under key (8 words or 32 bytes) and nonce (3 words): element i is keystream
+    words 4i..4i+3 (RFC 8439 section 2.3, block counter from 0) as a 128-bit little-endian
+    integer mod p."""
+    k, kp = _key_words(key)
+    if k is None:
+        raise R0HipError("fill_chacha20 needs a key")
+    nz, nzp = _h(nonce)
+    if nz.size != 3:
+        raise R0HipError("a ChaCha20 nonce is 3 words")
+    count = buf.nwords - offset if count is None else count
+    if offset < 0 or count < 0 or offset + count > buf.nwords:
+        raise R0HipError("fill_chacha20: range outside the buffer")
+    check(lib().r0hip_fill_chacha20(buf.ptr + 4 * offset, count, kp, nzp))
+
+
+def prove_recursion_keyed(hal, po2, ctrl, wom, cycles, iops, key, stream_id, seal_cap=1 << 24):
+    """r0hip_prove_recursion_keyed: prove_recursion with the ZK noise drawn from the ChaCha20
+    stream of `key` (8 words or 32 bytes; None: 32 bytes of getrandom(2) for this call) and
+    stream_id (a key must never meet the same stream_id twice). Returns (seal, mix)."""
+    w, c, i = _trace(wom, cycles, iops)
+    k, kp = _key_words(key)
+    seal = np.zeros(seal_cap, dtype=np.uint32)
+    n = C.c_size_t(0)
+    mix = np.zeros(20, dtype=np.uint32)
+    check(lib().r0hip_prove_recursion_keyed(hal.suite, po2, ctrl.ptr, w.ctypes.data_as(u32p), w.size // 4,
+                                            c.ctypes.data_as(u32p), c.size // 2, i.ctypes.data_as(u32p), i.size // 4,
+                                            kp, stream_id, seal.ctypes.data_as(u32p), seal_cap, C.byref(n),
+                                            mix.ctypes.data_as(u32p)))
+    return seal[: n.value].copy(), mix
+
+
 class RawBuffer(C.Structure):
     """struct r0hip_raw_buffer (RawBuffer, rv32im-sys/src/lib.rs:63-69)"""
     _fields_ = [("buf", C.c_void_p), ("rows", C.c_size_t), ("cols", C.c_size_t), ("checked", C.c_bool)]
@@ -706,6 +758,147 @@ def prove_trace_segments(hal, po2, traces, in_flight=2, seal_cap=1 << 22, verify
     if verify:
         assert all(j.verified for j in jobs)
     return [(seal[: j.seal_len].copy(), mix) for j, seal, mix in zip(jobs, seals, mixes)]
+
+
+class RecursionInput(C.Structure):
+    """struct r0hip_recursion_input (include/r0hip.h): one recursion job's host arrays"""
+    _fields_ = [("h_ctrl", C.c_void_p), ("h_wom", C.c_void_p), ("n_wom", C.c_size_t), ("h_cycles", C.c_void_p),
+                ("n_cycles", C.c_size_t), ("h_iops", C.c_void_p), ("n_iops", C.c_size_t),
+                ("h_code_roots", C.c_void_p), ("n_code_roots", C.c_size_t)]
+
+
+class WorkerJobStruct(C.Structure):
+    """struct r0hip_worker_job (include/r0hip.h)"""
+    _fields_ = [("kind", C.c_uint32), ("suite", C.c_int), ("po2", C.c_uint32), ("trace", TraceInput),
+                ("h_bigint", C.c_void_p), ("n_bigint", C.c_size_t), ("recursion", RecursionInput),
+                ("user", C.c_void_p), ("h_seal", C.c_void_p), ("seal_cap", C.c_size_t), ("seal_len", C.c_size_t),
+                ("h_mix_out", C.c_void_p), ("error", C.c_void_p), ("verified", C.c_int), ("verify_ms", C.c_double),
+                ("prove_ms", C.c_double), ("ticket", C.c_uint64)]
+
+
+JOB_RV32IM_TRACE, JOB_RECURSION = 0, 1
+
+
+class Worker:
+    """The GPU worker (r0hip_worker_*): a persistent queue that takes rv32im trace jobs of any
+    po2 <= max_po2 and recursion jobs as they arrive, proves them pipelined over `in_flight`
+    provers, checks every receipt (verify) and hands the results back in completion order.
+
+        with Worker(hal, max_po2=20, in_flight=3) as w:
+            t0 = w.submit_trace(job, 20)
+            t1 = w.submit_recursion(17, ctrl, wom, cycles, iops, code_roots=roots)
+            ticket, seal, mix, error, verify_ms, prove_ms = w.wait(10.0)
+
+    noise_key (8 words or 32 bytes) makes the recursion jobs' ZK noise reproducible and is for
+    tests only: the default (None) draws an OS key for the worker's lifetime. The inputs of a
+    job are kept alive here until wait() returns it. Leaving the `with` block destroys the
+    worker, which first runs everything submitted to completion."""
+
+    def __init__(self, hal, max_po2, in_flight=2, verify=True, noise_key=None, seal_cap=1 << 22):
+        self.hal, self.verify, self.seal_cap = hal, bool(verify), seal_cap
+        self._pending = {}  # address of the job struct -> (struct, seal, mix, inputs)
+        k, kp = _key_words(noise_key)
+        h = C.c_void_p()
+        check(lib().r0hip_worker_create(C.byref(h), max_po2, in_flight, int(self.verify), kp))
+        self._h = h
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def close(self):
+        """r0hip_worker_destroy: run what was submitted, join the threads, free the sets. Results
+        not yet waited for are dropped (their error strings are freed)."""
+        h, self._h = getattr(self, "_h", None), None
+        if h is None or not h.value:
+            return
+        err = lib().r0hip_worker_destroy(h)
+        for job, _seal, _mix, _keep in self._pending.values():
+            if job.error:
+                libc_free(job.error)
+        self._pending.clear()
+        check(err)
+
+    def _handle(self):
+        if self._h is None or not self._h.value:
+            raise R0HipError("the worker is closed")
+        return self._h
+
+    def _submit(self, job, mix_words, keep):
+        seal = np.zeros(self.seal_cap, dtype=np.uint32)
+        mix = np.zeros(mix_words, dtype=np.uint32)
+        job.h_seal, job.seal_cap, job.h_mix_out = seal.ctypes.data, self.seal_cap, mix.ctypes.data
+        check(lib().r0hip_worker_submit(self._handle(), C.byref(job)))
+        self._pending[C.addressof(job)] = (job, seal, mix, keep)
+        return int(job.ticket)
+
+    def submit_trace(self, trace, po2, suite=None):
+        """queue one rv32im prove_core from a TraceJob at segment size 2^po2; returns its ticket"""
+        job = WorkerJobStruct()
+        job.kind, job.po2 = JOB_RV32IM_TRACE, po2
+        job.suite = self.hal.suite if suite is None else (SUITES[suite] if isinstance(suite, str) else int(suite))
+        job.trace = trace.struct
+        if trace.backs is not None:
+            job.h_bigint, job.n_bigint = C.cast(trace.backs, C.c_void_p).value, len(trace.backs)
+        return self._submit(job, 36, trace)
+
+    def submit_recursion(self, po2, ctrl, wom, cycles, iops, code_roots=None, suite=None):
+        """queue one recursion proof from the program's control group (23 x 2^po2 host words)
+        and its preflight; code_roots: the allow-list (8 words each) its receipt check applies.
+        Returns its ticket, which is also the stream_id of its ZK noise."""
+        w, c, i = _trace(wom, cycles, iops)
+        ct = ctrl if isinstance(ctrl, np.ndarray) and ctrl.dtype == np.uint32 and ctrl.flags.c_contiguous \
+            else np.ascontiguousarray(ctrl, dtype=np.uint32)
+        if ct.size != 23 << po2:
+            raise R0HipError(f"the control group of a po2={po2} recursion job is {23 << po2} words, got {ct.size}")
+        roots = np.ascontiguousarray(np.zeros(0, np.uint32) if code_roots is None else code_roots,
+                                     dtype=np.uint32).reshape(-1)
+        if roots.size % 8:
+            raise R0HipError("code_roots holds 8 words per root")
+        job = WorkerJobStruct()
+        job.kind, job.po2 = JOB_RECURSION, po2
+        job.suite = self.hal.suite if suite is None else (SUITES[suite] if isinstance(suite, str) else int(suite))
+        job.recursion = RecursionInput(ct.ctypes.data, w.ctypes.data if w.size else None, w.size // 4,
+                                       c.ctypes.data if c.size else None, c.size // 2,
+                                       i.ctypes.data if i.size else None, i.size // 4,
+                                       roots.ctypes.data if roots.size else None, roots.size // 8)
+        return self._submit(job, 20, (ct, w, c, i, roots))
+
+    def outstanding(self):
+        """jobs submitted and not yet returned by wait()"""
+        return len(self._pending)
+
+    def wait(self, timeout_s=None):
+        """The next finished job in completion order as (ticket, seal, mix, error or None,
+        verify_ms, prove_ms), or None when the timeout passed (None waits without limit, 0
+        polls) or nothing is outstanding. With verify, a job without an error that the
+        verifier did not pass raises R0HipError."""
+        done = C.c_void_p()
+        ms = -1 if timeout_s is None else max(0, int(round(timeout_s * 1000)))
+        check(lib().r0hip_worker_wait(self._handle(), C.byref(done), ms))
+        if not done.value:
+            return None
+        entry = self._pending.pop(done.value, None)
+        if entry is None:
+            raise R0HipError("r0hip_worker_wait returned a job this Worker did not submit")
+        job, seal, mix, _keep = entry
+        error = None
+        if job.error:
+            error = C.cast(job.error, C.c_char_p).value.decode()
+            libc_free(job.error)
+            job.error = None
+        if self.verify and error is None and not job.verified:
+            raise R0HipError(f"job {job.ticket} came back without an error and without a verified receipt")
+        return int(job.ticket), seal[: job.seal_len].copy(), mix, error, job.verify_ms, job.prove_ms
 
 
 def prove_segments(hal, circuit, po2, witnesses, version=None, in_flight=2, seal_cap=1 << 24):
