@@ -12,7 +12,12 @@
  *   - sizes/counts are 64-bit element counts (the CUDA ABI's u32 overflows at po2=24);
  *   - every call is complete when it returns (cuda.h:77-100 semantics): results are
  *     visible to the next call and to D2H copies. Work is queued on one HIP stream
- *     per process; r0hip_prove_segment runs whole proofs without per-op syncs.
+ *     per host thread; r0hip_prove_segment runs whole proofs without per-op syncs.
+ *   - a thread may opt into deferred completion (r0hip_set_deferred below), the CUDA HAL's
+ *     stream-ordered behaviour. Each prototype carries its kind: [queues] = device-only, returns
+ *     with its work queued on the thread's stream while the mode is on; [drains] = hands data or
+ *     a verdict to the host, always complete on return; [host-only] = no device work. With the
+ *     mode off (the default) every [queues] call drains as well.
  * Suites: R0HIP_POSEIDON2 = 0, R0HIP_SHA256 = 1, R0HIP_POSEIDON254 = 2 (zkp/src/core/hash/mod.rs:90-100;
  * the CUDA HAL's CudaHashPoseidon254, zkp/src/hal/cuda.rs:179-233).
  */
@@ -31,28 +36,61 @@ extern "C" {
 #define R0HIP_POSEIDON254 2
 
 /* ---- device / memory (replaces the `cust` crate; zkp/src/hal/cuda.rs:235-381,397-421) ---- */
+/* [drains] */
 const char* r0hip_init(int device_ordinal);                       /* sppark_init (sys/src/cuda.rs:20) */
+/* [drains] */
 const char* r0hip_device_info(char* name, size_t name_cap, uint64_t* total_mem);
+/* [queues] */
 const char* r0hip_alloc(void** d_ptr, size_t bytes);
+/* [queues] */
 const char* r0hip_free(void* d_ptr);
+/* [queues] */
 const char* r0hip_memset32(void* d_dst, uint32_t value, size_t count); /* alloc_elem_init (hal/mod.rs:72-83) */
+/* [drains] */
 const char* r0hip_memcpy_h2d(void* d_dst, const void* h_src, size_t bytes);
+/* [drains] */
 const char* r0hip_memcpy_d2h(void* h_dst, const void* d_src, size_t bytes);
+/* [queues] */
 const char* r0hip_memcpy_d2d(void* d_dst, const void* d_src, size_t bytes);
 /* page-locked host memory for full-rate witness uploads (cust's LockedBuffer role) */
+/* [drains] */
 const char* r0hip_host_alloc(void** h_ptr, size_t bytes);
+/* [drains] */
 const char* r0hip_host_free(void* h_ptr);
+/* [drains] */
 const char* r0hip_synchronize(void);
+/* Completion mode of the calling host thread (thread-local, like the stream; 0 on every new
+ * thread, and the library's own pipeline and worker threads never change it). on != 0: the
+ * [queues] entry points return after enqueueing, in call order on the thread's stream; results
+ * are visible to the thread's later calls and to the host after any [drains] call. *was (may be
+ * NULL) receives the previous mode. Turning the mode off drains the thread's stream first and
+ * returns an asynchronous error of the queued work, if any. Rules while the mode is on:
+ *   - host arrays (h_*) passed to a [queues] call are consumed before it returns;
+ *   - a host-side validation failure is returned by the failing call itself, which drains, and
+ *     the mode stays on; an asynchronous HIP error is returned by the next [drains] call;
+ *   - a buffer may be freed by this thread at any time (its block is reused in stream order),
+ *     but only after the work that OTHER threads queued on it has been synchronised there;
+ *   - before the thread exits it calls r0hip_synchronize or r0hip_set_deferred(0, ..): a thread
+ *     that exits with work queued leaks its device blocks, stream and staging arena. */
+/* [host-only] */
+const char* r0hip_set_deferred(int on, int* was);
+/* The calling thread's entry-point calls so far, no device work: out[0] = [queues] and [drains]
+ * calls made, out[1] = those that drained the stream before returning, out[2] = those that
+ * returned with their work only queued. */
+/* [host-only] */
+const char* r0hip_call_stats(uint64_t out[3]);
 void r0hip_free_error(const char* err);
 /* A device-to-host copy that runs beside the caller's later calls, for a HAL's host mirrors
  * (hal_hip.rs: a Merkle node heap, read node by node by MerkleTreeProver::prove, merkle.rs:
  * 108-140). The copy goes on a process-wide copy stream; d_src is read as the caller's earlier
- * calls left it (every call is complete on return), and must not be written or freed until the
- * copy finished. *h_copy = a handle for r0hip_copy_finish, or NULL when the copy is already
+ * calls left it (in deferred mode the copy stream waits for the calls still queued), and must
+ * not be written or freed until the copy finished. *h_copy = a handle for r0hip_copy_finish, or NULL when the copy is already
  * done (bytes == 0, or h_dst is not r0hip_host_alloc memory: then it is copied before return).
  * r0hip_copy_finish: *done = 1 when the bytes are in h_dst (the handle is then released; a
  * NULL handle is done), 0 if not yet (only with block == 0). */
+/* [queues] */
 const char* r0hip_memcpy_d2h_start(void* h_dst, const void* d_src, size_t bytes, void** h_copy);
+/* [host-only] */
 const char* r0hip_copy_finish(void* h_copy, int block, int* done);
 
 /* ---- NTT family (sppark_batch_* in sys/src/cuda.rs:22-46; CPU semantics cpu.rs:305-408) ----
@@ -61,60 +99,80 @@ const char* r0hip_copy_finish(void* h_copy, int block, int* done);
  * non-canonical input word is not reduced there. */
 /* expand each of `count` polys of 2^(lg_out-expand_bits) bit-reversed coeffs into out (count x 2^lg_out)
  * and evaluate: Hal::batch_expand_into_evaluate_ntt (hal/mod.rs:102-108; cuda.rs:529-570) */
+/* [queues] */
 const char* r0hip_batch_expand_into_evaluate_ntt(uint32_t* d_out, const uint32_t* d_in, size_t count,
                                                  uint32_t lg_out, uint32_t expand_bits);
 /* Hal::batch_interpolate_ntt (hal/mod.rs:110; cuda.rs:572-590 -> sppark_batch_iNTT) */
+/* [queues] */
 const char* r0hip_batch_interpolate_ntt(uint32_t* d_io, size_t count, uint32_t lg_size);
 /* Hal::zk_shift (hal/mod.rs:123; cuda.rs:690-708 -> sppark_batch_zk_shift) */
+/* [queues] */
 const char* r0hip_zk_shift(uint32_t* d_io, size_t count, uint32_t lg_size);
 /* Hal::batch_bit_reverse (risc0_zkp_cuda_batch_bit_reverse, ffi.cu:89-91) */
+/* [queues] */
 const char* r0hip_batch_bit_reverse(uint32_t* d_io, size_t count, uint32_t lg_size);
 
 /* ---- polynomial ops ---- */
 /* risc0_zkp_cuda_batch_evaluate_any (ffi.cu:93-101): out[k] = sum_i coeffs[which[k]][i] * xs[k]^i */
+/* [queues] */
 const char* r0hip_batch_evaluate_any(uint32_t* d_out, const uint32_t* d_coeffs, size_t poly_count,
                                      uint32_t lg_poly_size, const uint32_t* d_which, const uint32_t* d_xs,
                                      size_t eval_count);
 /* risc0_zkp_cuda_mix_poly_coeffs (ffi.cu:79-87); mix_start / mix are host FpExt (4 words) */
+/* [queues] */
 const char* r0hip_mix_poly_coeffs(uint32_t* d_out, const uint32_t* d_in, const uint32_t* h_combos,
                                   const uint32_t* h_mix_start, const uint32_t* h_mix, size_t input_size,
                                   size_t count);
 /* risc0_zkp_cuda_fri_fold (ffi.cu:75-77): out is 4 x count, in is 4 x 16 x count (SoA planes) */
+/* [queues] */
 const char* r0hip_fri_fold(uint32_t* d_out, const uint32_t* d_in, const uint32_t* h_mix, size_t count);
 /* risc0_zkp_cuda_combos_prepare (ffi.cu:125-143); host arrays, CHECK_SIZE = 16 */
+/* [queues] */
 const char* r0hip_combos_prepare(uint32_t* d_combos, const uint32_t* h_coeff_u, size_t combo_count,
                                  size_t cycles, const uint32_t* h_reg_sizes, const uint32_t* h_reg_combo_ids,
                                  size_t reg_count, const uint32_t* h_mix);
 /* supra_poly_divide (sys/src/cuda.rs:74-79): in-place division of a poly of `size` FpExt by (x - z);
  * h_remainder receives the remainder (Hal::combos_divide asserts it is zero, hal/mod.rs:236-257) */
+/* [drains] */
 const char* r0hip_poly_divide(uint32_t* d_poly, size_t size, uint32_t* h_remainder, const uint32_t* h_z);
 /* Hal::combos_divide batched over all combos: chunk i divides combos[i*cycles..] by each z in
  * h_pows[h_begin[i]..h_begin[i+1]); *bad_chunk = first chunk with a nonzero remainder or -1 */
+/* [drains] */
 const char* r0hip_combos_divide(uint32_t* d_combos, size_t nchunks, const uint32_t* h_pows,
                                 const uint32_t* h_begin, size_t cycles, int64_t* bad_chunk);
 
 /* ---- element-wise (ffi.cu:27-73) ---- */
+/* [queues] */
 const char* r0hip_eltwise_add_elem(uint32_t* d_out, const uint32_t* d_a, const uint32_t* d_b, size_t count);
+/* [queues] */
 const char* r0hip_eltwise_copy_elem(uint32_t* d_out, const uint32_t* d_in, size_t count);
+/* [queues] */
 const char* r0hip_eltwise_zeroize_elem(uint32_t* d_io, size_t count);
 /* out (4 x count SoA) = sum over to_add of in (to_add x count FpExt) */
+/* [queues] */
 const char* r0hip_eltwise_sum_extelem(uint32_t* d_out, const uint32_t* d_in, size_t to_add, size_t count);
+/* [queues] */
 const char* r0hip_eltwise_copy_elem_slice(uint32_t* d_into, const uint32_t* d_from, size_t from_rows,
                                           size_t from_cols, size_t from_offset, size_t from_stride,
                                           size_t into_offset, size_t into_stride);
+/* [queues] */
 const char* r0hip_gather_sample(uint32_t* d_dst, const uint32_t* d_src, size_t idx, size_t size, size_t stride);
 /* gather_sample straight to the host: h_dst[i] = d_src[idx + i*stride], i < size (no CUDA
  * counterpart). For a HAL whose gather_sample destination is read back before the device uses it
  * (MerkleTreeProver::prove's sample, merkle.rs:111-129: gather_sample, then view): one kernel,
  * one copy and one sync instead of a device allocation, gather_sample, view and free. */
+/* [drains] */
 const char* r0hip_gather_sample_host(uint32_t* h_dst, const uint32_t* d_src, size_t idx, size_t size,
                                      size_t stride);
 /* CSR scatter (ffi.cu:108-114): index has cycles+1 entries */
+/* [queues] */
 const char* r0hip_scatter(uint32_t* d_into, const uint32_t* d_index, const uint32_t* d_offsets,
                           const uint32_t* d_values, size_t cycles);
+/* [queues] */
 const char* r0hip_prefix_products(uint32_t* d_io, size_t count);
 /* not a reference symbol: synthetic witness words (uniform canonical BabyBear values from a
  * counter hash of seed and index) for benches and tests at full size */
+/* [queues] */
 const char* r0hip_fill_uniform(uint32_t* d_out, size_t count, uint64_t seed);
 /* not a reference symbol: keyed noise words, the generator of r0hip_prove_recursion_keyed. The
  * ChaCha20 keystream of RFC 8439 section 2.3 (20 rounds, 32-bit block counter starting at 0)
@@ -123,6 +181,7 @@ const char* r0hip_fill_uniform(uint32_t* d_out, size_t count, uint64_t seed);
  * mod p = 15 * 2^27 + 1 and stored as the raw word (bias below 2^-96), so block b yields
  * elements 4b..4b+3 and the words do not depend on how the kernel is launched. count <= 2^34.
  * The key is passed to the kernel by value: no device copy of it is made. */
+/* [queues] */
 const char* r0hip_fill_chacha20(uint32_t* d_out, size_t count, const uint32_t* h_key, const uint32_t* h_nonce);
 
 /* ---- hashing (sppark_poseidon2_{rows,fold}, sppark_poseidon254_{rows,fold}, risc0_zkp_cuda_sha_{rows,fold};
@@ -131,19 +190,23 @@ const char* r0hip_fill_chacha20(uint32_t* d_out, size_t count, const uint32_t* h
  * canonical field words (< p): the Poseidon2 full rounds read a word as a signed 32-bit value,
  * which is its value mod p for any word below 2^31 (tests/native/field_equiv.cpp pins
  * [p, 2^31)) but not above. */
+/* [queues] */
 const char* r0hip_hash_rows(int suite, uint32_t* d_out, const uint32_t* d_matrix, size_t rows, size_t cols);
 /* io[output_size + i] = H(io[input_size + 2i], io[input_size + 2i + 1]) (cpu.rs:569-581) */
+/* [queues] */
 const char* r0hip_hash_fold(int suite, uint32_t* d_io, size_t input_size, size_t output_size);
 /* A whole tree in one call: MerkleTreeProver::new's hash_rows into nodes[rows..2rows) and
  * hash_fold of every layer down to the root at nodes[1] (prove/merkle.rs:54-81); d_nodes
  * holds 2*rows digests, rows a power of two. Same words as those calls; the fused form knows
  * each layer's height, so Poseidon2 and SHA-256 layers over all-zero rows store the zero-subtree digests
  * instead of hashing them. */
+/* [queues] */
 const char* r0hip_merkle_tree(int suite, uint32_t* d_nodes, const uint32_t* d_matrix, size_t rows, size_t cols);
 
 /* ---- circuits (risc0_circuit_{rv32im,recursion}_cuda_eval_check) ---- */
 /* circuit: "rv32im" | "recursion". groups[g] = evaluated register group g (accum=0, code=1, data=2),
  * d_check = 4 x 4*2^po2, h_poly_mix = the poly_mix FpExt (powers are expanded on the host) */
+/* [drains] */
 const char* r0hip_eval_check(const char* circuit, uint32_t* d_check, const uint32_t* const* d_groups,
                              const uint32_t* d_mix, const uint32_t* d_global, const uint32_t* h_poly_mix,
                              uint32_t po2);
@@ -153,6 +216,7 @@ const char* r0hip_eval_check(const char* circuit, uint32_t* d_check, const uint3
  * Witness groups are device buffers (column-major, 2^po2 rows); d_global (output_size words) is
  * zeroized in place; h_mix_out (optional) receives the mix values drawn from the transcript.
  * The seal (Vec<u32>) is written to h_seal; *seal_len is its length in words. */
+/* [drains] */
 const char* r0hip_prove_segment(const char* circuit, int suite, uint32_t po2, const uint32_t* d_code,
                                 const uint32_t* d_data, const uint32_t* d_accum, uint32_t* d_global,
                                 int write_version, uint32_t version, uint32_t* h_seal, size_t seal_cap,
@@ -175,6 +239,7 @@ typedef struct r0hip_bigint_back {
  * record into h_states. h_mix is the whole rv32im mix (36 words; the last 4 are the final
  * mix). Fails as the reference does on an EqZero whose goal is nonzero ("Invalid eqz in
  * bigint accum"). Host-only. */
+/* [host-only] */
 const char* r0hip_rv32im_bigint_accum_states(const uint32_t* h_mix, const r0hip_bigint_back* h_backs, size_t n,
                                              size_t rows, uint32_t* h_states);
 /* The same states computed on the device (BigIntAccum::step, byte_poly.rs:381-470, as three
@@ -184,6 +249,7 @@ const char* r0hip_rv32im_bigint_accum_states(const uint32_t* h_mix, const r0hip_
  * function writes. n <= rows <= 2^26. Fails with the host function's messages, at the earliest
  * record in trace order that fails any check. Always takes the device path; n == 0 is a no-op.
  * Complete on return. */
+/* [drains] */
 const char* r0hip_rv32im_bigint_accum_states_device(uint32_t* d_states, const uint32_t* h_mix,
                                                     const r0hip_bigint_back* h_backs, size_t n, size_t rows);
 /* The states above scattered into accum columns 0..11 (BigIntAccumState::offsets,
@@ -192,6 +258,7 @@ const char* r0hip_rv32im_bigint_accum_states_device(uint32_t* d_states, const ui
  * on, the states are computed on the device (as r0hip_rv32im_bigint_accum_states_device) and
  * scattered from device memory; below that the host loop is faster and its states are
  * uploaded. The words and the errors are the same either way. */
+/* [queues] */
 const char* r0hip_rv32im_bigint_accum_inject(uint32_t* d_accum, size_t rows, const uint32_t* h_mix,
                                              const r0hip_bigint_back* h_backs, size_t n);
 
@@ -207,6 +274,7 @@ const char* r0hip_rv32im_bigint_accum_inject(uint32_t* d_accum, size_t rows, con
  * accumulated over work_cycles cycles (rv32im: the preflight cycle count, 2^po2; recursion:
  * work_cycles), INVALID words are zeroized, and the group is committed. The other arguments
  * are r0hip_prove_segment's. */
+/* [drains] */
 const char* r0hip_prove_segment_accum(const char* circuit, int suite, uint32_t po2, const uint32_t* d_code,
                                       const uint32_t* d_data, uint32_t* d_accum, size_t work_cycles,
                                       const r0hip_bigint_back* h_bigint, size_t n_bigint, uint32_t* d_global,
@@ -217,6 +285,7 @@ const char* r0hip_prove_segment_accum(const char* circuit, int suite, uint32_t p
  * prefix sums of the last 4 accum columns over rows [0, last_cycle), then every row adds the
  * previous row's prefix values to the machine columns [23, cols - 4). d_accum is the accum
  * group, column-major with `rows` rows, after the per-cycle phase (r0hip_rv32im_accum runs both). */
+/* [queues] */
 const char* r0hip_rv32im_accum_finalize(uint32_t* d_accum, size_t rows, size_t cols, size_t last_cycle);
 /* ---- rv32im witness side: the whole accumulation (risc0_circuit_rv32im_cuda_accum,
  * rv32im-sys/kernels/cuda/ffi.cu:362-514; CPU risc0_circuit_rv32im_cpu_accum, ffi.cpp:313-368):
@@ -225,6 +294,7 @@ const char* r0hip_rv32im_accum_finalize(uint32_t* d_accum, size_t rows, size_t c
  * the data group (211 columns), d_accum the accum group (cols = 103) as the prover allocates
  * it (every word INVALID, 0xFFFFFFFF); d_global (90 words) and d_mix (36 words) as in
  * AccumBuffers (witgen.h). Columns are `rows` long. */
+/* [queues] */
 const char* r0hip_rv32im_accum(const uint32_t* d_data, uint32_t* d_accum, const uint32_t* d_global,
                                const uint32_t* d_mix, size_t rows, size_t cols, size_t last_cycle);
 
@@ -261,6 +331,7 @@ typedef struct r0hip_raw_preflight_trace {
   uint32_t bigint_bytes_len;
   uint32_t table_split_cycle;
 } r0hip_raw_preflight_trace;
+/* [drains] */
 const char* r0hip_rv32im_witgen(uint32_t mode, const r0hip_raw_exec_buffers* buffers,
                                 const r0hip_raw_preflight_trace* preflight, uint32_t cycles);
 
@@ -277,6 +348,7 @@ const char* r0hip_rv32im_witgen(uint32_t mode, const r0hip_raw_exec_buffers* buf
  * accumulation on the device. Seal and mix out as r0hip_prove_segment. */
 /* Host arrays of 64 KiB or more that lie inside r0hip_host_alloc blocks are copied to the
  * device directly; others are staged through the calling thread's page-locked arena. */
+/* [drains] */
 const char* r0hip_prove_segment_trace(int suite, uint32_t po2, uint32_t mode, const uint32_t* h_global,
                                       const uint32_t* h_inj_index, size_t inj_rows, const uint32_t* h_inj_offsets,
                                       const uint32_t* h_inj_values, const r0hip_raw_preflight_trace* preflight,
@@ -287,6 +359,7 @@ const char* r0hip_prove_segment_trace(int suite, uint32_t po2, uint32_t mode, co
  * injector arrays, and d_preflight's cycles / txns / bigint_bytes are DEVICE pointers; the
  * struct itself and h_bigint are on the host): what the benchmark times, inputs in HBM.
  * Injector offsets outside the data group are skipped. */
+/* [drains] */
 const char* r0hip_prove_segment_trace_resident(int suite, uint32_t po2, uint32_t mode, const uint32_t* d_global,
                                                const uint32_t* d_inj_index, size_t inj_rows,
                                                const uint32_t* d_inj_offsets, const uint32_t* d_inj_values,
@@ -302,6 +375,7 @@ const char* r0hip_prove_segment_trace_resident(int suite, uint32_t po2, uint32_t
  * total_cycles rows (a power of two); d_mix holds the mix values, d_global the globals. Cells
  * no step writes are left as they were (the reference leaves them INVALID for the caller to
  * zeroize, witgen.rs:172-175). */
+/* [queues] */
 const char* r0hip_recursion_accum(const uint32_t* d_ctrl, const uint32_t* d_global, const uint32_t* d_data,
                                   const uint32_t* d_mix, uint32_t* d_accum, size_t work_cycles,
                                   size_t total_cycles);
@@ -318,6 +392,7 @@ const char* r0hip_recursion_accum(const uint32_t* d_ctrl, const uint32_t* d_glob
  * cycles in order), the WOM argument sorted and scanned, injectWomBacks, step_verify_mem.
  * Fails with the reference's message on a failed check ("eqz failed at: ..."). ZK noise and
  * zeroize stay the caller's (witgen.rs:101-123). */
+/* [drains] */
 const char* r0hip_recursion_witgen(const uint32_t* d_ctrl, uint32_t* d_data, uint32_t* d_global, size_t total_cycles,
                                    const uint32_t* h_wom, size_t n_wom, const uint32_t* h_cycles, size_t n_cycles,
                                    const uint32_t* h_iops, size_t n_iops);
@@ -330,6 +405,7 @@ const char* r0hip_recursion_witgen(const uint32_t* d_ctrl, uint32_t* d_data, uin
  * DETERMINISTIC, for tests and benches: the noise is a counter hash of the 64-bit noise_seed,
  * not a random draw, so a seal made by this call is not zero-knowledge. The call to ship is
  * r0hip_prove_recursion_keyed below. */
+/* [drains] */
 const char* r0hip_prove_recursion(int suite, uint32_t po2, const uint32_t* d_ctrl, const uint32_t* h_wom, size_t n_wom,
                                   const uint32_t* h_cycles, size_t n_cycles, const uint32_t* h_iops, size_t n_iops,
                                   uint64_t noise_seed, uint32_t* h_seal, size_t seal_cap, size_t* seal_len,
@@ -343,6 +419,7 @@ const char* r0hip_prove_recursion(int suite, uint32_t po2, const uint32_t* d_ctr
  * getrandom(2) drawn for this call (the call fails if the OS gives none; there is no weaker
  * source). A caller's key must never meet the same stream_id twice. Host copies of the key are
  * wiped when the call returns. */
+/* [drains] */
 const char* r0hip_prove_recursion_keyed(int suite, uint32_t po2, const uint32_t* d_ctrl, const uint32_t* h_wom,
                                         size_t n_wom, const uint32_t* h_cycles, size_t n_cycles,
                                         const uint32_t* h_iops, size_t n_iops, const uint32_t* h_key,
@@ -375,6 +452,7 @@ typedef struct r0hip_segment_job {
   uint32_t* h_mix_out;
   const char* error;
 } r0hip_segment_job;
+/* [drains] */
 const char* r0hip_prove_segments(const char* circuit, int suite, uint32_t po2, int write_version, uint32_t version,
                                  r0hip_segment_job* jobs, size_t njobs, uint32_t in_flight);
 
@@ -414,6 +492,7 @@ typedef struct r0hip_trace_job {
   double prove_ms;                    /* out: host milliseconds from a prover taking the job to its
                                          seal in host memory (the wait for its upload included) */
 } r0hip_trace_job;
+/* [drains] */
 const char* r0hip_prove_trace_segments(int suite, uint32_t po2, r0hip_trace_job* jobs, size_t njobs,
                                        uint32_t in_flight, int verify);
 
@@ -483,10 +562,14 @@ typedef struct r0hip_worker_job {
                                          seal in host memory (the wait for its upload included) */
   uint64_t ticket;                    /* out: submission number, from 0 */
 } r0hip_worker_job;
+/* [drains] */
 const char* r0hip_worker_create(r0hip_worker** out, uint32_t max_po2, uint32_t in_flight, int verify,
                                 const uint32_t* h_noise_key);
+/* [host-only] */
 const char* r0hip_worker_submit(r0hip_worker* w, r0hip_worker_job* job);
+/* [host-only] */
 const char* r0hip_worker_wait(r0hip_worker* w, r0hip_worker_job** done, int64_t timeout_ms);
+/* [drains] */
 const char* r0hip_worker_destroy(r0hip_worker* w);
 
 /* ---- seal verification (risc0/zkp/src/verify/mod.rs:500-560 `verify`, with merkle.rs:79-186,
@@ -501,26 +584,32 @@ const char* r0hip_worker_destroy(r0hip_worker* w);
  * control-id allow-list (zkvm/src/receipt/succinct.rs:143-157). Host-only: needs no GPU and
  * no r0hip_init. Returns NULL when the seal verifies (po2 of the segment in *po2_out, if
  * non-NULL), else the failed check. */
+/* [host-only] */
 const char* r0hip_verify_seal(const char* circuit, int suite, const uint32_t* seal, size_t seal_len,
                               const uint32_t* h_code_roots, size_t n_code_roots, uint32_t* h_code_root_out,
                               uint32_t* po2_out);
 /* TESTING ONLY — never use it to accept a receipt. r0hip_verify_seal without the validity
  * equation and without a code-root check, for seals of synthetic witnesses (which do not
  * satisfy the constraints) in the parity tests. */
+/* [host-only] */
 const char* r0hip_testing_verify_seal_structure(const char* circuit, int suite, const uint32_t* seal,
                                                 size_t seal_len, uint32_t* po2_out);
 /* PolyExt::poly_ext of the circuit (its generated poly_ext.rs, called at mod.rs:356-386): the
  * constraint polynomial at the out-of-domain point. h_mix (mix_size) and h_global
  * (output_size) are Montgomery words, h_eval_u one FpExt (4 words) per tap in tap order,
  * h_poly_mix one FpExt; the result FpExt goes to h_out. Host-only. */
+/* [host-only] */
 const char* r0hip_poly_ext(const char* circuit, const uint32_t* h_mix, const uint32_t* h_global,
                            const uint32_t* h_eval_u, const uint32_t* h_poly_mix, uint32_t* h_out);
 
 /* kernel-level timing with HIP events on the library stream: enable, run, then read
  * "name=total_ms:calls:alg_bytes;..." (alg_bytes = algorithmic HBM bytes) */
+/* [drains] */
 const char* r0hip_set_kernel_timing(int on);
+/* [drains] */
 const char* r0hip_kernel_times(char* buf, size_t cap);
 /* per-phase device timings (ms) of the last r0hip_prove_segment, as "name=ms;..." */
+/* [drains] */
 const char* r0hip_last_profile(char* buf, size_t cap);
 
 /* Device-memory accounting, replacing the reference HAL's MemoryTracker
@@ -528,11 +617,14 @@ const char* r0hip_last_profile(char* buf, size_t cap);
  * risc0/zkvm/examples/datasheet.rs:251). out[5] = {live bytes (buffers handed out),
  * peak live bytes, reserved bytes (held from hipMalloc incl. the free pool), peak
  * reserved bytes, number of hipMalloc calls}. Peaks are since the last reset. Host-only. */
+/* [host-only] */
 const char* r0hip_mem_stats(uint64_t* out);
+/* [host-only] */
 const char* r0hip_mem_reset_peak(void);
 /* Release the idle device memory the library holds: the calling thread's free pool and
  * the blocks exited threads left (pool and scratch). Blocks in use are untouched. For a
  * caller switching segment sizes, and for tests that need a clean pool. */
+/* [drains] */
 const char* r0hip_trim(void);
 
 #ifdef __cplusplus

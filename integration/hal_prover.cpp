@@ -165,6 +165,19 @@ struct Profile {
   }
 };
 thread_local std::string g_profile;
+thread_local bool g_deferred = false;  // halp_set_deferred
+
+// r0hip_set_deferred around one proof: on for its calls, the caller's mode (drained) after it
+struct DeferredScope {
+  int was = 0;
+  bool active;
+  explicit DeferredScope(bool on) : active(on) {
+    if (active) ok(r0hip_set_deferred(1, &was));
+  }
+  ~DeferredScope() {
+    if (active) free(const_cast<char*>(r0hip_set_deferred(was, nullptr)));  // the proof's reads have drained its errors
+  }
+};
 
 FpExt fe_words(const uint32_t* w) { return FpExt{{w[0], w[1], w[2], w[3]}}; }
 
@@ -536,6 +549,11 @@ const char* halp_last_profile(char* buf, size_t cap) {
   return nullptr;
 }
 
+const char* halp_set_deferred(int on) {
+  g_deferred = on != 0;
+  return nullptr;
+}
+
 const char* halp_prove_segment(const char* circuit, const halp_taps* taps, int suite, uint32_t po2,
                                const uint32_t* d_code, const uint32_t* d_data, uint32_t* d_accum, uint32_t* d_global,
                                int accum_mode, size_t work_cycles, const r0hip_bigint_back* h_bigint, size_t n_bigint,
@@ -543,6 +561,7 @@ const char* halp_prove_segment(const char* circuit, const halp_taps* taps, int s
                                uint32_t* h_mix_out) {
   return wrap([&] {
     if (!circuit || !taps || !d_code || !d_data || !d_accum || !d_global) throw std::runtime_error("halp: null argument");
+    DeferredScope deferred_scope(g_deferred);
     Profile prof;
     std::vector<uint32_t> mix;
     auto seal = prove(circuit, *taps, suite, po2, d_code, d_data, d_accum, d_global, accum_mode, work_cycles, h_bigint,
@@ -559,6 +578,7 @@ const char* halp_prove_trace(const halp_taps* taps, int suite, uint32_t po2, uin
                              size_t* seal_len, uint32_t* h_mix_out) {
   return wrap([&] {
     if (!taps || !h_global || !h_inj_index || !preflight) throw std::runtime_error("halp: null argument");
+    DeferredScope deferred_scope(g_deferred);
     Profile prof;
     const size_t n = size_t(1) << po2;
     // WitnessGenerator::new (witgen/mod.rs:106-176): the groups INVALID, the injector scattered

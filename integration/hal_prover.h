@@ -5,8 +5,9 @@
  * witgen/mod.rs:106-223) restated in C++ over ONLY the per-op symbols of include/r0hip.h, one
  * call per Hal / CircuitHal method, exactly as integration/rust/hal_hip.rs and
  * circuit_hal_hip.rs bind them. This is what a Rust `HipHal` behind `risc0_zkp::hal::Hal`
- * delivers (every call synchronous, `has_unified_memory() = false`, so Merkle openings are one
- * device-to-host copy per node), measured without Rust, which this image lacks.
+ * delivers (every call synchronous unless halp_set_deferred asks for the stream-ordered mode,
+ * `has_unified_memory() = false`, so Merkle openings are one device-to-host copy per node),
+ * measured without Rust, which this image lacks.
  *
  * Not part of the product: libr0hip_halprover.so links libr0hip.so and calls no fused entry
  * point (tests/test_abi.py checks its undefined symbols). Host-side hashing and the transcript
@@ -41,6 +42,14 @@ typedef struct halp_taps {
 
 /* Per-phase host milliseconds of the last call on this thread, "name=ms;..." */
 const char* halp_last_profile(char* buf, size_t cap);
+
+/* Completion mode of the proofs this thread drives (thread-local, default 0). on != 0: each
+ * halp_prove_* call turns on r0hip_set_deferred for its duration and restores the caller's mode
+ * (draining the stream) before it returns, as a HipHal built with_deferred(true) runs. The call
+ * sequence is the same: the device-only Hal calls then return with their work queued, and the
+ * host waits only where the Prover reads (get_at, view, to_vec, remainders) and in eval_check
+ * and the witness generator. */
+const char* halp_set_deferred(int on);
 
 /* The prove core over device witness groups (Prover::commit_group x3 + finalize), with the
  * accumulation between the mix draw and the accum commit when accum_mode != 0:

@@ -35,6 +35,8 @@ def lib():
         _lib.halp_prove_trace.restype = vp
         _lib.halp_prove_trace.argtypes = [vp, C.c_int, C.c_uint32, C.c_uint32, vp, vp, sz, vp, vp, vp, vp, sz, vp, sz,
                                           C.POINTER(sz), vp]
+        _lib.halp_set_deferred.restype = vp
+        _lib.halp_set_deferred.argtypes = [C.c_int]
         _lib.halp_last_profile.restype = vp
         _lib.halp_last_profile.argtypes = [C.c_char_p, sz]
     return _lib
@@ -75,8 +77,10 @@ def last_profile():
 
 
 def prove_segment(hal, circuit, po2, code, data, accum, glob, accum_mode=0, work_cycles=0, bigint_records=None,
-                  version=None, seal_cap=1 << 22):
-    """halp_prove_segment over device buffers (risc0_amd Buffers); returns (seal, mix)"""
+                  version=None, seal_cap=1 << 22, deferred=False):
+    """halp_prove_segment over device buffers (risc0_amd Buffers); returns (seal, mix).
+    deferred: the proof's per-op calls run in r0hip_set_deferred mode (halp_set_deferred)"""
+    lib().halp_set_deferred(int(deferred))
     from risc0_amd.hal import bigint_backs
     taps = CircuitTaps(circuit)
     backs = bigint_backs(bigint_records)
@@ -91,8 +95,10 @@ def prove_segment(hal, circuit, po2, code, data, accum, glob, accum_mode=0, work
     return seal[: n.value].copy(), mix
 
 
-def prove_trace(hal, po2, job, seal_cap=1 << 22):
-    """halp_prove_trace over a risc0_amd.TraceJob (its host arrays); returns (seal, mix)"""
+def prove_trace(hal, po2, job, seal_cap=1 << 22, deferred=False):
+    """halp_prove_trace over a risc0_amd.TraceJob (its host arrays); returns (seal, mix).
+    deferred: as prove_segment"""
+    lib().halp_set_deferred(int(deferred))
     taps = CircuitTaps("rv32im")
     t = job.struct
     seal = np.zeros(seal_cap, np.uint32)

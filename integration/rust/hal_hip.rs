@@ -329,6 +329,7 @@ pub struct HipHal<HS: HipHash> {
     suite: HashSuite<BabyBear>,
     _lock: ReentrantMutexGuard<'static, ()>,
     _hs: PhantomData<HS>,
+    deferred: bool,
 }
 
 pub type HipHalPoseidon2 = HipHal<HipHashPoseidon2>;
@@ -343,9 +344,34 @@ impl<HS: HipHash> Default for HipHal<HS> {
 
 impl<HS: HipHash> HipHal<HS> {
     pub fn new() -> Self {
+        Self::with_deferred(false)
+    }
+
+    /// A HAL whose device-only calls return once their work is queued on this thread's stream
+    /// (r0hip_set_deferred), as the CUDA HAL's do; `false` is `new()`, every call complete on
+    /// return. The mode belongs to the constructing thread, which the HAL cannot leave (it holds
+    /// the device lock's guard), and is turned off, draining the stream, when the HAL is
+    /// dropped. The calls that still synchronise are the ones that hand something to the host:
+    /// r0hip_memcpy_d2h and r0hip_memcpy_h2d (Buffer::view, view_mut, get_at, to_vec,
+    /// copy_from_*), r0hip_gather_sample_host, r0hip_poly_divide and r0hip_combos_divide (their
+    /// remainders), r0hip_eval_check, the witness generators (r0hip_rv32im_witgen,
+    /// r0hip_recursion_witgen), r0hip_host_alloc / r0hip_host_free and r0hip_synchronize. A
+    /// buffer shared with another thread is dropped only after that thread's queued work on it
+    /// has been synchronised there.
+    pub fn with_deferred(deferred: bool) -> Self {
         let _lock = device_lock().lock();
         check(unsafe { r0hip_init(device_ordinal()) });
-        Self { suite: HS::new_suite(), _lock, _hs: PhantomData }
+        if deferred {
+            check(unsafe { r0hip_set_deferred(1, std::ptr::null_mut()) });
+        }
+        Self { suite: HS::new_suite(), _lock, _hs: PhantomData, deferred }
+    }
+
+    /// This thread's per-op calls so far: (made, drained before returning, returned queued).
+    pub fn call_stats(&self) -> (u64, u64, u64) {
+        let mut out = [0u64; 3];
+        check(unsafe { r0hip_call_stats(out.as_mut_ptr()) });
+        (out[0], out[1], out[2])
     }
 
     /// Name and memory of the bound device (for logs; cust's Device::name role).
@@ -354,6 +380,16 @@ impl<HS: HipHash> HipHal<HS> {
         let mut mem = 0u64;
         check(unsafe { r0hip_device_info(name.as_mut_ptr(), name.len(), &mut mem) });
         (unsafe { CStr::from_ptr(name.as_ptr()) }.to_string_lossy().into_owned(), mem)
+    }
+}
+
+impl<HS: HipHash> Drop for HipHal<HS> {
+    fn drop(&mut self) {
+        // a deferred thread drains before it can exit (a thread that exits with work queued
+        // leaks its device blocks); the result of a drop is not reported
+        if self.deferred {
+            unsafe { r0hip_free_error(r0hip_set_deferred(0, std::ptr::null_mut())) };
+        }
     }
 }
 

@@ -144,6 +144,10 @@ unsafe extern "C" {
     pub fn r0hip_host_alloc(h_ptr: *mut *mut c_void, bytes: usize) -> *const c_char;
     pub fn r0hip_host_free(h_ptr: *mut c_void) -> *const c_char;
     pub fn r0hip_synchronize() -> *const c_char;
+    // the calling thread's completion mode (device-only calls return with their work queued) and
+    // its call counters {calls, drained, queued}
+    pub fn r0hip_set_deferred(on: c_int, was: *mut c_int) -> *const c_char;
+    pub fn r0hip_call_stats(out: *mut u64) -> *const c_char;
     pub fn r0hip_free_error(err: *const c_char);
     // a device-to-host copy beside later calls (the HAL's node-heap mirrors, hal_hip.rs)
     pub fn r0hip_memcpy_d2h_start(h_dst: *mut c_void, d_src: *const c_void, bytes: usize,

@@ -1,7 +1,10 @@
 // C ABI (include/r0hip.h): the symbols a Rust `HipHal` binds in place of the
 // reference's risc0_zkp_cuda_* / sppark_* / cust calls. Each entry point runs its
-// kernels on the library stream and returns only when they have finished
-// (risc0/sys/kernels/zkp/cuda/cuda.h:77-100 semantics); errors come back as a
+// kernels on the calling thread's stream and returns only when they have finished
+// (risc0/sys/kernels/zkp/cuda/cuda.h:77-100 semantics), unless the thread has asked for
+// deferred completion (r0hip_set_deferred): then the device-only entry points (wrap_dev)
+// return with their work queued, as the stream-ordered CUDA HAL's do, and the entry points
+// that hand data or a verdict to the host (wrap) drain first. Errors come back as a
 // malloc'd string (risc0/sys/src/lib.rs:53-75 convention).
 #include "../../include/r0hip.h"
 
@@ -39,22 +42,40 @@ using namespace r0;
 namespace {
 // The call's work is complete on return, and the calling thread's idle device memory goes back
 // to the shared pool (release_thread_memory), so a caller's thread holds none between calls.
+// `may_defer`: a device-only entry point (wrap_dev below). In the calling thread's deferred mode
+// (r0hip_set_deferred) it returns with its work queued: no drain, and the thread keeps its
+// memory, which queued work may still use. A failed call drains in either mode.
 template <typename F>
-const char* wrap(F f) {
+const char* wrap(F f, bool may_defer = false) {
+  const bool queue = may_defer && deferred_mode();
   try {
+    if (queue) call_will_queue();
     f();
+    if (queue) {
+      call_queued();
+      return nullptr;
+    }
     HIP_OK(hipStreamSynchronize(stream()));
   } catch (const std::exception& e) {
     drain_after_error();
+    call_drained();
     release_thread_memory();
     return strdup(e.what());
   } catch (...) {
     drain_after_error();
+    call_drained();
     release_thread_memory();
     return strdup("r0hip: unknown error");
   }
+  call_drained();
   release_thread_memory();
   return nullptr;
+}
+// Device-only entry points: device pointers and by-value scalars in, nothing handed to the host.
+// Host arrays they take are consumed before they return (copied, or staged by upload_async).
+template <typename F>
+const char* wrap_dev(F f) {
+  return wrap(f, true);
 }
 // host-only entry points: no stream, no device
 template <typename F>
@@ -101,13 +122,13 @@ const char* r0hip_device_info(char* name, size_t name_cap, uint64_t* total_mem) 
 }
 
 const char* r0hip_alloc(void** d_ptr, size_t bytes) {
-  return wrap([&] { *d_ptr = dev_alloc(bytes); });
+  return wrap_dev([&] { *d_ptr = dev_alloc(bytes); });
 }
 const char* r0hip_free(void* d_ptr) {
-  return wrap([&] { dev_free(d_ptr); });
+  return wrap_dev([&] { dev_free(d_ptr); });
 }
 const char* r0hip_memset32(void* d_dst, uint32_t value, size_t count) {
-  return wrap([&] { HIP_OK(hipMemsetD32Async(d_dst, int(value), count, stream())); });
+  return wrap_dev([&] { HIP_OK(hipMemsetD32Async(d_dst, int(value), count, stream())); });
 }
 const char* r0hip_memcpy_h2d(void* d_dst, const void* h_src, size_t bytes) {
   return wrap([&] { upload(d_dst, h_src, bytes); });
@@ -116,7 +137,7 @@ const char* r0hip_memcpy_d2h(void* h_dst, const void* d_src, size_t bytes) {
   return wrap([&] { download(h_dst, d_src, bytes); });
 }
 const char* r0hip_memcpy_d2d(void* d_dst, const void* d_src, size_t bytes) {
-  return wrap([&] { HIP_OK(hipMemcpyAsync(d_dst, d_src, bytes, hipMemcpyDeviceToDevice, stream())); });
+  return wrap_dev([&] { HIP_OK(hipMemcpyAsync(d_dst, d_src, bytes, hipMemcpyDeviceToDevice, stream())); });
 }
 const char* r0hip_host_alloc(void** h_ptr, size_t bytes) {
   return wrap([&] { *h_ptr = host_alloc(bytes); });
@@ -126,6 +147,18 @@ const char* r0hip_host_free(void* h_ptr) {
 }
 const char* r0hip_synchronize(void) {
   return wrap([] {});
+}
+const char* r0hip_set_deferred(int on, int* was) {
+  return wrap_nosync([&] {
+    if (was) *was = deferred_mode() ? 1 : 0;
+    set_deferred_mode(on != 0);
+  });
+}
+const char* r0hip_call_stats(uint64_t* out) {
+  return wrap_nosync([&] {
+    R0_REQUIRE(out != nullptr, "r0hip_call_stats: null output");
+    call_stats(out);
+  });
 }
 
 namespace {
@@ -138,7 +171,7 @@ struct PendingCopy {  // r0hip_memcpy_d2h_start's handle: the copy's completion 
 }  // namespace
 
 const char* r0hip_memcpy_d2h_start(void* h_dst, const void* d_src, size_t bytes, void** h_copy) {
-  return wrap([&] {
+  return wrap_dev([&] {
     R0_REQUIRE(h_copy, "r0hip_memcpy_d2h_start: h_copy is NULL");
     *h_copy = nullptr;
     if (!bytes) return;
@@ -150,6 +183,9 @@ const char* r0hip_memcpy_d2h_start(void* h_dst, const void* d_src, size_t bytes,
     auto pc = std::make_unique<PendingCopy>();
     HIP_OK(hipEventCreateWithFlags(&pc->ev, hipEventDisableTiming));
     const hipStream_t cs = copy_stream();
+    // after deferred calls the kernels that produce d_src may still be queued on this thread's
+    // stream: the copy stream waits for them (nothing to wait for when the last call drained)
+    order_after_thread_work(cs);
     HIP_OK(hipMemcpyAsync(h_dst, d_src, bytes, hipMemcpyDeviceToHost, cs));
     HIP_OK(hipEventRecord(pc->ev, cs));
     *h_copy = pc.release();
@@ -175,34 +211,34 @@ void r0hip_free_error(const char* err) { free(const_cast<char*>(err)); }
 
 const char* r0hip_batch_expand_into_evaluate_ntt(uint32_t* d_out, const uint32_t* d_in, size_t count, uint32_t lg_out,
                                                  uint32_t expand_bits) {
-  return wrap([&] {
+  return wrap_dev([&] {
     R0_REQUIRE(lg_out >= expand_bits && lg_out <= 27, "bad NTT size");
     ntt_evaluate(stream(), d_out, d_in, count, lg_out, expand_bits);
   });
 }
 const char* r0hip_batch_interpolate_ntt(uint32_t* d_io, size_t count, uint32_t lg_size) {
-  return wrap([&] {
+  return wrap_dev([&] {
     R0_REQUIRE(lg_size <= 27, "bad NTT size");
     ntt_interpolate(stream(), d_io, count, lg_size, false);
   });
 }
 const char* r0hip_zk_shift(uint32_t* d_io, size_t count, uint32_t lg_size) {
-  return wrap([&] { zk_shift(stream(), d_io, count, lg_size); });
+  return wrap_dev([&] { zk_shift(stream(), d_io, count, lg_size); });
 }
 const char* r0hip_batch_bit_reverse(uint32_t* d_io, size_t count, uint32_t lg_size) {
-  return wrap([&] { bit_reverse(stream(), d_io, count, lg_size); });
+  return wrap_dev([&] { bit_reverse(stream(), d_io, count, lg_size); });
 }
 
 const char* r0hip_batch_evaluate_any(uint32_t* d_out, const uint32_t* d_coeffs, size_t poly_count,
                                      uint32_t lg_poly_size, const uint32_t* d_which, const uint32_t* d_xs,
                                      size_t eval_count) {
-  return wrap([&] { batch_evaluate_any(stream(), d_coeffs, poly_count, lg_poly_size, d_which, d_xs, d_out, eval_count); });
+  return wrap_dev([&] { batch_evaluate_any(stream(), d_coeffs, poly_count, lg_poly_size, d_which, d_xs, d_out, eval_count); });
 }
 
 const char* r0hip_mix_poly_coeffs(uint32_t* d_out, const uint32_t* d_in, const uint32_t* h_combos,
                                   const uint32_t* h_mix_start, const uint32_t* h_mix, size_t input_size,
                                   size_t count) {
-  return wrap([&] {
+  return wrap_dev([&] {
     std::vector<uint32_t> combos(h_combos, h_combos + input_size);
     uint32_t* d = static_cast<uint32_t*>(scratch(input_size * 4 + 16, kSlotApiMixWhich));
     upload_async(d, combos.data(), input_size * 4);
@@ -211,13 +247,13 @@ const char* r0hip_mix_poly_coeffs(uint32_t* d_out, const uint32_t* d_in, const u
 }
 
 const char* r0hip_fri_fold(uint32_t* d_out, const uint32_t* d_in, const uint32_t* h_mix, size_t count) {
-  return wrap([&] { fri_fold(stream(), d_out, d_in, fe(h_mix), count); });
+  return wrap_dev([&] { fri_fold(stream(), d_out, d_in, fe(h_mix), count); });
 }
 
 const char* r0hip_combos_prepare(uint32_t* d_combos, const uint32_t* h_coeff_u, size_t combo_count, size_t cycles,
                                  const uint32_t* h_reg_sizes, const uint32_t* h_reg_combo_ids, size_t reg_count,
                                  const uint32_t* h_mix) {
-  return wrap([&] {
+  return wrap_dev([&] {
     size_t width = 1;
     for (size_t r = 0; r < reg_count; r++) width = std::max<size_t>(width, h_reg_sizes[r]);
     std::vector<FpExt> deltas((combo_count + 1) * width, fe_zero());
@@ -277,27 +313,27 @@ const char* r0hip_combos_divide(uint32_t* d_combos, size_t nchunks, const uint32
 }
 
 const char* r0hip_eltwise_add_elem(uint32_t* d_out, const uint32_t* d_a, const uint32_t* d_b, size_t count) {
-  return wrap([&] { eltwise_add(stream(), d_out, d_a, d_b, count); });
+  return wrap_dev([&] { eltwise_add(stream(), d_out, d_a, d_b, count); });
 }
 const char* r0hip_eltwise_copy_elem(uint32_t* d_out, const uint32_t* d_in, size_t count) {
-  return wrap([&] { eltwise_copy(stream(), d_out, d_in, count); });
+  return wrap_dev([&] { eltwise_copy(stream(), d_out, d_in, count); });
 }
 const char* r0hip_eltwise_zeroize_elem(uint32_t* d_io, size_t count) {
-  return wrap([&] { eltwise_zeroize(stream(), d_io, count); });
+  return wrap_dev([&] { eltwise_zeroize(stream(), d_io, count); });
 }
 const char* r0hip_eltwise_sum_extelem(uint32_t* d_out, const uint32_t* d_in, size_t to_add, size_t count) {
-  return wrap([&] { eltwise_sum_extelem(stream(), d_out, d_in, count, to_add); });
+  return wrap_dev([&] { eltwise_sum_extelem(stream(), d_out, d_in, count, to_add); });
 }
 const char* r0hip_eltwise_copy_elem_slice(uint32_t* d_into, const uint32_t* d_from, size_t from_rows,
                                           size_t from_cols, size_t from_offset, size_t from_stride,
                                           size_t into_offset, size_t into_stride) {
-  return wrap([&] {
+  return wrap_dev([&] {
     copy_elem_slice(stream(), d_into, d_from, from_rows, from_cols, from_offset, from_stride, into_offset,
                     into_stride);
   });
 }
 const char* r0hip_gather_sample(uint32_t* d_dst, const uint32_t* d_src, size_t idx, size_t size, size_t stride) {
-  return wrap([&] { gather_sample(stream(), d_dst, d_src, idx, size, stride); });
+  return wrap_dev([&] { gather_sample(stream(), d_dst, d_src, idx, size, stride); });
 }
 const char* r0hip_gather_sample_host(uint32_t* h_dst, const uint32_t* d_src, size_t idx, size_t size,
                                      size_t stride) {
@@ -311,19 +347,19 @@ const char* r0hip_gather_sample_host(uint32_t* h_dst, const uint32_t* d_src, siz
 }
 const char* r0hip_scatter(uint32_t* d_into, const uint32_t* d_index, const uint32_t* d_offsets,
                           const uint32_t* d_values, size_t cycles) {
-  return wrap([&] { scatter(stream(), d_into, d_index, d_offsets, d_values, cycles); });
+  return wrap_dev([&] { scatter(stream(), d_into, d_index, d_offsets, d_values, cycles); });
 }
 const char* r0hip_prefix_products(uint32_t* d_io, size_t count) {
-  return wrap([&] { prefix_products(stream(), d_io, count); });
+  return wrap_dev([&] { prefix_products(stream(), d_io, count); });
 }
 const char* r0hip_rv32im_accum_finalize(uint32_t* d_accum, size_t rows, size_t cols, size_t last_cycle) {
   // kUserAccumSplit = kLayout_TopAccum.columns[0].col (rv32im-sys/kernels/cxx/ffi.cpp:52,
   // layout.cpp.inc:6993-6999): the first machine accumulator column
-  return wrap([&] { rv32im_accum_finalize(stream(), d_accum, rows, cols, 23, last_cycle); });
+  return wrap_dev([&] { rv32im_accum_finalize(stream(), d_accum, rows, cols, 23, last_cycle); });
 }
 const char* r0hip_rv32im_accum(const uint32_t* d_data, uint32_t* d_accum, const uint32_t* d_global,
                                const uint32_t* d_mix, size_t rows, size_t cols, size_t last_cycle) {
-  return wrap([&] { rv32im_accum(stream(), d_data, d_accum, d_global, d_mix, rows, cols, last_cycle); });
+  return wrap_dev([&] { rv32im_accum(stream(), d_data, d_accum, d_global, d_mix, rows, cols, last_cycle); });
 }
 const char* r0hip_rv32im_bigint_accum_states(const uint32_t* h_mix, const r0hip_bigint_back* h_backs, size_t n,
                                              size_t rows, uint32_t* h_states) {
@@ -344,16 +380,16 @@ const char* r0hip_rv32im_bigint_accum_states_device(uint32_t* d_states, const ui
 }
 const char* r0hip_rv32im_bigint_accum_inject(uint32_t* d_accum, size_t rows, const uint32_t* h_mix,
                                              const r0hip_bigint_back* h_backs, size_t n) {
-  return wrap([&] {
+  return wrap_dev([&] {
     R0_REQUIRE(d_accum && h_mix, "r0hip_rv32im_bigint_accum_inject: null argument");
-    stage_reset();
+    if (!deferred_mode()) stage_reset();  // it drains; the deferred arena recycles itself
     rv32im_bigint_inject(stream(), d_accum, rows, h_mix, h_backs, n);
   });
 }
 const char* r0hip_recursion_accum(const uint32_t* d_ctrl, const uint32_t* d_global, const uint32_t* d_data,
                                   const uint32_t* d_mix, uint32_t* d_accum, size_t work_cycles,
                                   size_t total_cycles) {
-  return wrap([&] {
+  return wrap_dev([&] {
     R0_REQUIRE(d_ctrl && d_global && d_data && d_mix && d_accum, "r0hip_recursion_accum: null argument");
     recursion_accum(stream(), d_ctrl, d_global, d_data, d_mix, d_accum, work_cycles, total_cycles);
   });
@@ -633,7 +669,7 @@ const char* r0hip_prove_recursion_keyed(int suite, uint32_t po2, const uint32_t*
 
 const char* r0hip_fill_chacha20(uint32_t* d_out, size_t count, const uint32_t* h_key, const uint32_t* h_nonce) {
   ChaChaKey k;
-  const char* err = wrap([&] {
+  const char* err = wrap_dev([&] {
     R0_REQUIRE((d_out || !count) && h_key && h_nonce, "r0hip_fill_chacha20: null argument");
     memcpy(k.key, h_key, sizeof k.key);
     memcpy(k.nonce, h_nonce, sizeof k.nonce);
@@ -644,23 +680,23 @@ const char* r0hip_fill_chacha20(uint32_t* d_out, size_t count, const uint32_t* h
 }
 
 const char* r0hip_fill_uniform(uint32_t* d_out, size_t count, uint64_t seed) {
-  return wrap([&] { fill_uniform(stream(), d_out, count, seed); });
+  return wrap_dev([&] { fill_uniform(stream(), d_out, count, seed); });
 }
 
 const char* r0hip_hash_rows(int suite, uint32_t* d_out, const uint32_t* d_matrix, size_t rows, size_t cols) {
-  return wrap([&] {
+  return wrap_dev([&] {
     R0_REQUIRE(suite >= 0 && suite <= 2, "unknown hash suite");
     hash_rows(stream(), suite, d_out, d_matrix, rows, cols);
   });
 }
 const char* r0hip_hash_fold(int suite, uint32_t* d_io, size_t input_size, size_t output_size) {
-  return wrap([&] {
+  return wrap_dev([&] {
     R0_REQUIRE(suite >= 0 && suite <= 2, "unknown hash suite");
     hash_fold(stream(), suite, d_io, input_size, output_size);
   });
 }
 const char* r0hip_merkle_tree(int suite, uint32_t* d_nodes, const uint32_t* d_matrix, size_t rows, size_t cols) {
-  return wrap([&] {
+  return wrap_dev([&] {
     R0_REQUIRE(suite >= 0 && suite <= 2, "unknown hash suite");
     R0_REQUIRE(rows > 0 && (rows & (rows - 1)) == 0, "merkle_tree: rows must be a power of two");
     merkle_tree(stream(), suite, d_nodes, d_matrix, rows, cols);

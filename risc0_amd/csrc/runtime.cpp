@@ -46,6 +46,7 @@ std::map<int, std::multimap<size_t, void*>> g_scratch_orphans;
 std::thread::id g_main_thread;
 std::vector<hipStream_t> g_free_streams;  // streams of exited threads (drained)
 std::vector<Stage> g_free_stages;         // their pinned upload arenas
+std::vector<hipEvent_t> g_free_events;    // their ordering events (order_after_thread_work)
 // MemStats counters (see mem_stats)
 std::atomic<uint64_t> g_mem_live{0}, g_peak_live{0}, g_reserved{0}, g_peak_reserved{0}, g_mallocs{0};
 
@@ -55,6 +56,15 @@ struct ThreadCtx {
   std::multimap<size_t, void*> pool;  // free blocks by size, last used on `stream`
   Stage stage;
   std::vector<uint8_t*> stage_old;
+  // completion mode (r0hip_set_deferred): device-only entry points return with their work queued
+  bool deferred = false;
+  // an entry point has returned without draining and nothing has drained the stream since: the
+  // pool and scratch blocks, the arena and the stream may still be in use by queued work
+  bool pending = false;
+  // inside an entry point that will return without draining (call_will_queue .. call_queued)
+  bool queueing = false;
+  hipEvent_t order_ev = nullptr;  // order_after_thread_work's, recorded again at each use
+  uint64_t calls = 0, calls_drained = 0, calls_queued = 0;  // r0hip_call_stats
   // the idle pool and scratch blocks to the shared lists (caller holds g_mu; stream drained)
   void hand_back_memory() {
     for (auto& kv : pool) g_orphans.emplace(kv.first, kv.second);
@@ -69,13 +79,18 @@ struct ThreadCtx {
   ~ThreadCtx() {
     // A worker thread hands its stream and memory over when it exits — no HIP calls
     // here (thread-exit destructors run after tools' per-thread state is gone). Every
-    // API call drains its stream before returning, so the blocks are idle. The main
-    // thread's context dies in process teardown and is left alone.
+    // API call of the default mode drains its stream before returning, so the blocks are
+    // idle. The main thread's context dies in process teardown and is left alone.
     if (!stream || std::this_thread::get_id() == g_main_thread) return;
+    // A deferred thread that exits without r0hip_synchronize / r0hip_set_deferred(0) may have
+    // work queued on all of it, and nothing here can wait for that work: its blocks, stream,
+    // arena and event are leaked, never reused.
+    if (pending) return;
     std::lock_guard<std::mutex> lk(g_mu);
     hand_back_memory();
     g_free_streams.push_back(stream);
     if (stage.base) g_free_stages.push_back(Stage{stage.base, stage.cap, 0});
+    if (order_ev) g_free_events.push_back(order_ev);
     // superseded arenas in stage_old are left allocated (rare: only after growth)
   }
 };
@@ -171,14 +186,77 @@ hipStream_t copy_stream() {
   return s;
 }
 
+namespace {
+// this thread's stream has just been drained: nothing of the thread's is in use by queued work
+void stream_drained() noexcept {
+  t_ctx.pending = false;
+  // deferred calls never call stage_reset, so their staged copies are released here (they have
+  // run); the default mode recycles the arena where it always did
+  if (t_ctx.deferred) t_ctx.stage.used = 0;
+}
+}  // namespace
+
 void drain_after_error() noexcept {
-  if (t_ctx.stream) (void)hipStreamSynchronize(t_ctx.stream);
+  if (!t_ctx.stream) return;
+  (void)hipStreamSynchronize(t_ctx.stream);
+  stream_drained();
 }
 
 void release_thread_memory() noexcept {
-  if (!t_ctx.stream) return;
+  if (!t_ctx.stream || t_ctx.pending) return;  // queued work may still use the blocks
   std::lock_guard<std::mutex> lk(g_mu);
   t_ctx.hand_back_memory();
+}
+
+bool deferred_mode() noexcept { return t_ctx.deferred; }
+
+bool set_deferred_mode(bool on) {
+  const bool was = t_ctx.deferred;
+  hipError_t e = hipSuccess;
+  if (was && !on && t_ctx.stream) {
+    e = hipStreamSynchronize(t_ctx.stream);
+    stream_drained();  // while the mode is still on: the arena is recycled
+    release_thread_memory();
+  }
+  t_ctx.deferred = on;
+  HIP_OK(e);
+  return was;
+}
+
+void call_will_queue() noexcept { t_ctx.queueing = true; }
+
+void call_drained() noexcept {
+  t_ctx.queueing = false;
+  stream_drained();
+  t_ctx.calls++;
+  t_ctx.calls_drained++;
+}
+
+void call_queued() noexcept {
+  t_ctx.queueing = false;
+  t_ctx.pending = true;
+  t_ctx.calls++;
+  t_ctx.calls_queued++;
+}
+
+void call_stats(uint64_t out[3]) noexcept {
+  out[0] = t_ctx.calls;
+  out[1] = t_ctx.calls_drained;
+  out[2] = t_ctx.calls_queued;
+}
+
+void order_after_thread_work(hipStream_t other) {
+  if (!t_ctx.pending) return;  // every earlier call drained: its results are in memory
+  if (!t_ctx.order_ev) {
+    std::lock_guard<std::mutex> lk(g_mu);
+    if (!g_free_events.empty()) {
+      t_ctx.order_ev = g_free_events.back();
+      g_free_events.pop_back();
+    }
+  }
+  if (!t_ctx.order_ev) HIP_OK(hipEventCreateWithFlags(&t_ctx.order_ev, hipEventDisableTiming));
+  HIP_OK(hipEventRecord(t_ctx.order_ev, t_ctx.stream));
+  HIP_OK(hipStreamWaitEvent(other, t_ctx.order_ev, 0));
 }
 
 const uint32_t* dev_table(const std::string& key, const std::function<std::vector<uint32_t>()>& gen) {
@@ -249,10 +327,20 @@ void* scratch(size_t bytes, int slot) {
 
 namespace {
 // `bytes` of this thread's page-locked arena (a new, larger arena when it is full; the old one
-// stays alive for copies still queued from it until stage_reset)
+// stays alive for copies still queued from it until stage_reset). Deferred mode has no
+// stage_reset between drains, so a full arena is drained and reused from its start, and only a
+// request larger than the whole arena replaces it (the old one is idle by then and is freed).
 uint8_t* stage_take(size_t bytes) {
   Stage& st = t_ctx.stage;
   size_t need = (bytes + 255) & ~size_t(255);
+  if (st.used + need > st.cap && t_ctx.deferred && st.base) {
+    HIP_OK(hipStreamSynchronize(t_ctx.stream));
+    st.used = 0;
+    if (need > st.cap) {
+      (void)hipHostFree(st.base);
+      st = Stage{};
+    }
+  }
   if (st.used + need > st.cap) {
     if (st.base) t_ctx.stage_old.push_back(st.base);
     size_t cap = std::max<size_t>(size_t(64) << 20, need * 2);
@@ -273,8 +361,9 @@ void upload_async(void* d_dst, const void* h_src, size_t bytes) {
   ensure_init();
   // source inside a live r0hip_host_alloc block: already page-locked, copy it directly (the
   // callers keep their sources alive until the stream has drained: every entry point that
-  // takes host arrays returns only after its work is done)
-  if (bytes >= (size_t(64) << 10) && host_pinned(h_src, bytes)) {
+  // takes host arrays returns only after its work is done; a call that will return with its
+  // work queued may return before the copy has run, so it stages every source)
+  if (!t_ctx.queueing && bytes >= (size_t(64) << 10) && host_pinned(h_src, bytes)) {
     HIP_OK(hipMemcpyAsync(d_dst, h_src, bytes, hipMemcpyHostToDevice, t_ctx.stream));
     return;
   }

@@ -144,12 +144,39 @@ void drain_after_error() noexcept;
 // keeps no device memory between calls.
 void release_thread_memory() noexcept;
 
+// Completion mode of the calling thread (r0hip_set_deferred; off on every new thread). While it
+// is on, the C ABI's device-only entry points return with their work queued on the thread's
+// stream, and the rules that rest on "every call drains" change as follows:
+//   - the thread's pool and scratch blocks stay with the thread (its stream orders their reuse)
+//     and go to the shared lists only at a return that drained: release_thread_memory does
+//     nothing while work is queued;
+//   - inside a call that will return queued, upload_async stages every source (the caller's
+//     array may die before the copy runs); the arena is recycled at each drain, and a full
+//     arena drains the stream and starts over instead of stacking a second one;
+//   - a thread that exits with work queued leaks its blocks, stream and arena (~ThreadCtx can
+//     make no HIP call), so a deferred thread synchronises before it exits.
+// set_deferred_mode returns the previous mode; turning the mode off drains the stream first (an
+// asynchronous error of the queued work is thrown, with the mode already off).
+bool deferred_mode() noexcept;
+bool set_deferred_mode(bool on);
+// An entry point that will return with its work queued says so before it does any work; every
+// entry point ends with the stream drained, or with work left queued (deferred mode).
+void call_will_queue() noexcept;
+void call_drained() noexcept;
+void call_queued() noexcept;
+void call_stats(uint64_t out[3]) noexcept;  // this thread's calls: all, drained, queued
+// Make stream `other` wait for the work this thread has queued so far (an event on the thread's
+// stream); nothing to do when the thread's last call drained.
+void order_after_thread_work(hipStream_t other);
+
 // Stream-ordered host->device upload through a pinned bump arena, so the caller's
 // host data may die immediately. The arena is recycled by stage_reset() (call only
 // when the stream is idle). Exception: a source of 64 KiB or more inside a live
 // r0hip_host_alloc block is copied to the device directly, with no staging, so it must
-// stay valid until the copy has run. Rule for every entry point that takes host arrays:
-// drain this thread's stream (or stage_reset) before returning to the caller.
+// stay valid until the copy has run (a call that returns queued never takes this path). Rule
+// for every entry point that takes host arrays: drain this thread's stream (or stage_reset)
+// before returning to the caller, or, for one that may return deferred, pass host data only
+// through upload_async.
 void upload_async(void* d_dst, const void* h_src, size_t bytes);
 void stage_reset();
 // Device-to-host copy in stream order, complete on return (this thread's stream is drained):

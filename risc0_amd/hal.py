@@ -7,6 +7,7 @@ reference's DualHal tests (risc0/zkp/src/hal/mod.rs:319-616). It is a thin
 ctypes layer: every operation runs in libr0hip.so on the GPU. There is no CPU
 fallback; a missing library or device raises.
 """
+import contextlib
 import ctypes as C
 import os
 
@@ -66,6 +67,8 @@ def _declare(L):
         "r0hip_testing_verify_seal_structure": [C.c_char_p, C.c_int, u32p, sz, C.POINTER(C.c_uint32)],
         "r0hip_poly_ext": [C.c_char_p, u32p, u32p, u32p, u32p, u32p],
         "r0hip_synchronize": [],
+        "r0hip_set_deferred": [C.c_int, C.POINTER(C.c_int)],
+        "r0hip_call_stats": [C.POINTER(C.c_uint64)],
         "r0hip_batch_expand_into_evaluate_ntt": [vp, vp, sz, C.c_uint32, C.c_uint32],
         "r0hip_batch_interpolate_ntt": [vp, sz, C.c_uint32],
         "r0hip_zk_shift": [vp, sz, C.c_uint32],
@@ -200,9 +203,30 @@ class HipHal:
     EXT_SIZE = 4
     CHECK_SIZE = 16
 
-    def __init__(self, hashfn="poseidon2", device=0):
+    def __init__(self, hashfn="poseidon2", device=0, deferred=False):
         self.suite = SUITES[hashfn] if isinstance(hashfn, str) else int(hashfn)
         check(lib().r0hip_init(device))
+        if deferred:
+            self.set_deferred(True)
+
+    # ---- completion mode of the calling thread (r0hip_set_deferred) ----
+    def set_deferred(self, on):
+        """Device-only calls of this thread return with their work queued (on) or complete
+        (off, the default); turning it off drains the thread's stream. Returns the previous
+        mode. Reads (to_numpy, combos_divide, eval_check, the prove_* calls) always drain. A
+        thread that turned it on turns it off, or synchronises, before it exits."""
+        was = C.c_int(0)
+        check(lib().r0hip_set_deferred(1 if on else 0, C.byref(was)))
+        return bool(was.value)
+
+    @contextlib.contextmanager
+    def deferred(self, on=True):
+        """`with hal.deferred():` the mode for a block of calls, restored (and drained) after it"""
+        was = self.set_deferred(on)
+        try:
+            yield self
+        finally:
+            self.set_deferred(was)
 
     # ---- allocation (hal/mod.rs:67-100) ----
     def alloc_elem(self, name, size):
@@ -1001,6 +1025,14 @@ def kernel_times():
             ms, calls, b, mm = v.split(":")
             out[k] = (float(ms), int(calls), float(b), float(mm))
     return out
+
+
+def call_stats():
+    """The calling thread's device entry-point calls (r0hip_call_stats): how many were made, how
+    many drained the stream before returning, how many returned with their work only queued."""
+    out = (C.c_uint64 * 3)()
+    check(lib().r0hip_call_stats(out))
+    return {"calls": int(out[0]), "drained": int(out[1]), "queued": int(out[2])}
 
 
 def mem_stats():
