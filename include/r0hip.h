@@ -164,6 +164,19 @@ const char* r0hip_gather_sample(uint32_t* d_dst, const uint32_t* d_src, size_t i
 /* [drains] */
 const char* r0hip_gather_sample_host(uint32_t* h_dst, const uint32_t* d_src, size_t idx, size_t size,
                                      size_t stride);
+/* The sibling paths of n Merkle openings straight to the host (no CUDA counterpart), for a HAL
+ * that keeps a node heap on the device only: MerkleTreeProver::prove (merkle.rs:108-140) reads
+ * one node per level with get_at, and this call fetches all of one opening's nodes, or those of
+ * many openings, with one kernel, one copy and one sync. d_nodes is a heap of heap_digests
+ * digests (8 words each) with the root at index 1, as r0hip_hash_fold and r0hip_merkle_tree
+ * write it. For j = h_idx[i], h_dst[(i*levels + k)*8 ..] receives nodes[j] for k = 0 and
+ * nodes[(j >> k) ^ 1] for 1 <= k < levels: the `other_idx` sequence of merkle.rs:131-138 after
+ * its first get_at(j). Checked on the host before any device work, the message naming the index:
+ * 1 <= j < heap_digests, levels >= 1, and for levels > 1 (j >> (levels-1)) >= 2. Duplicate
+ * indices are allowed; n == 0 does nothing. h_dst may be pageable or r0hip_host_alloc memory. */
+/* [drains] */
+const char* r0hip_merkle_paths_host(uint32_t* h_dst, const uint32_t* d_nodes, size_t heap_digests,
+                                    const uint64_t* h_idx, size_t n, size_t levels);
 /* CSR scatter (ffi.cu:108-114): index has cycles+1 entries */
 /* [queues] */
 const char* r0hip_scatter(uint32_t* d_into, const uint32_t* d_index, const uint32_t* d_offsets,

@@ -9,6 +9,7 @@
 // Python). The host holds what the reference host holds: the transcript, the out-of-domain
 // evaluations and the register polynomials.
 #include "hal_prover.h"
+#include "node_reads.h"
 
 #include <chrono>
 #include <cstdlib>
@@ -54,10 +55,15 @@ struct Buf {
   // mirror once it has landed and reads the one node synchronously until then (the root and top
   // layer right after the build). The Prover writes a node heap only while it builds the tree
   // (hash_rows, hash_fold), so a tree's ~50 x 17 openings cost one overlapped bulk copy (268 MB
-  // at po2=20, ~5 ms of PCIe) instead of one synchronous 13 us copy per node.
+  // at po2=20, ~5 ms of PCIe) instead of one synchronous 13 us copy per node. The mirror is an
+  // optimisation under a budget (node_reads.h: halp_set_mirror_budget): a heap that does not fit
+  // beside the process's live mirrors, or whose page-locked allocation fails, stays on the device
+  // only, and a one-digest get_at on it fetches its opening's whole sibling path in one call
+  // (r0hip_merkle_paths_host) into `path`, which the opening's following get_ats hit.
   mutable uint32_t* host = nullptr;
   mutable bool host_ok = false;
   mutable void* pending = nullptr;  // the mirror's copy in flight
+  mutable halp::PathCache path;     // the last opening read from an un-mirrored heap
   // gather_sample into a buffer with no device memory yet (hal_hip.rs DeviceAlloc::gathered):
   // the words are gathered straight to the host (r0hip_gather_sample_host) and read from there;
   // MerkleTreeProver::prove's sample is only viewed, so it never gets device memory
@@ -69,7 +75,8 @@ struct Buf {
     p = static_cast<uint32_t*>(d);
   }
   Buf(Buf&& o) noexcept
-      : p(o.p), words(o.words), host(o.host), host_ok(o.host_ok), pending(o.pending), gathered(std::move(o.gathered)) {
+      : p(o.p), words(o.words), host(o.host), host_ok(o.host_ok), pending(o.pending), path(std::move(o.path)),
+        gathered(std::move(o.gathered)) {
     o.p = nullptr;
     o.host = nullptr;
     o.pending = nullptr;
@@ -80,6 +87,7 @@ struct Buf {
     std::swap(host, o.host);
     std::swap(host_ok, o.host_ok);
     std::swap(pending, o.pending);
+    std::swap(path, o.path);
     std::swap(gathered, o.gathered);
     return *this;
   }
@@ -102,7 +110,7 @@ struct Buf {
   ~Buf() {
     settle();
     if (p) free(const_cast<char*>(r0hip_free(p)));  // a drop never fails the proof
-    if (host) free(const_cast<char*>(r0hip_host_free(host)));
+    if (host) halp::ledger().release(host, words * 4);
   }
   // wait out a mirror copy in flight (before the buffer is written or freed)
   void settle() const noexcept {
@@ -114,20 +122,21 @@ struct Buf {
   void written() {
     settle();
     host_ok = false;
+    path.clear();
   }
   void mirror_start() {
     written();
-    if (!host) {
-      void* h = nullptr;
-      ok(r0hip_host_alloc(&h, words * 4));
-      host = static_cast<uint32_t*>(h);
-    }
+    if (!host) host = static_cast<uint32_t*>(halp::ledger().acquire(words * 4));
+    if (!host) return;  // over the budget, or no page-locked memory: get_at fetches paths
+    halp::ledger().started++;
     void* c = nullptr;
     ok(r0hip_memcpy_d2h_start(host, p, words * 4, &c));
     pending = c;
     host_ok = true;  // valid once `pending` has finished
   }
-  // n words at off: from the landed mirror, else one synchronous copy
+  // n words at off: from the landed mirror; else one digest below the root of a heap that has
+  // no mirror with its opening's path (the root, node 1, has none: one node either way); else,
+  // and while a mirror's copy is in flight, one synchronous copy
   const uint32_t* at(size_t off, size_t n, uint32_t* one) const {
     if (host_ok && pending) {
       int done = 0;
@@ -137,6 +146,7 @@ struct Buf {
       if (!done) pending = c;
     }
     if (host_ok && !pending) return host + off;
+    if (!host_ok && n == 8 && off % 8 == 0 && off >= 16) return path.get(p, words / 8, off / 8);
     ok(r0hip_memcpy_d2h(one, p + off, n * 4));
     return one;
   }
@@ -551,6 +561,22 @@ const char* halp_last_profile(char* buf, size_t cap) {
 
 const char* halp_set_deferred(int on) {
   g_deferred = on != 0;
+  return nullptr;
+}
+
+const char* halp_set_mirror_budget(uint64_t bytes) {
+  halp::ledger().budget = bytes;
+  return nullptr;
+}
+
+const char* halp_mirror_stats(uint64_t out[5]) {
+  if (!out) return strdup("halp_mirror_stats: null output");
+  halp::ledger().stats(out);
+  return nullptr;
+}
+
+const char* halp_reset_mirror_stats(void) {
+  halp::ledger().reset_stats();
   return nullptr;
 }
 

@@ -6,7 +6,8 @@
  * call per Hal / CircuitHal method, exactly as integration/rust/hal_hip.rs and
  * circuit_hal_hip.rs bind them. This is what a Rust `HipHal` behind `risc0_zkp::hal::Hal`
  * delivers (every call synchronous unless halp_set_deferred asks for the stream-ordered mode,
- * `has_unified_memory() = false`, so Merkle openings are one device-to-host copy per node),
+ * `has_unified_memory() = false`, so Merkle openings read node by node: from a host mirror of
+ * the heap under a budget, else one path fetch per opening, halp_set_mirror_budget),
  * measured without Rust, which this image lacks.
  *
  * Not part of the product: libr0hip_halprover.so links libr0hip.so and calls no fused entry
@@ -50,6 +51,21 @@ const char* halp_last_profile(char* buf, size_t cap);
  * host waits only where the Prover reads (get_at, view, to_vec, remainders) and in eval_check
  * and the witness generator. */
 const char* halp_set_deferred(int on);
+
+/* get_at on a Merkle node heap (MerkleTreeProver::prove, merkle.rs:108-140) reads a page-locked
+ * host mirror of the whole heap, 256 * 2^po2 bytes for each of a proof's four big trees. The
+ * mirrors are an optimisation under a process-wide budget, 4 GiB unless set here: a heap is
+ * mirrored only if it fits beside the mirrors alive at that moment and its page-locked
+ * allocation succeeds. A heap that is not mirrored stays on the device only, and each of its
+ * openings costs one r0hip_merkle_paths_host call (its first get_at fetches the whole sibling
+ * path, the following ones hit a per-buffer cache). The seal is the same either way. */
+const char* halp_set_mirror_budget(uint64_t bytes);
+/* Since the last reset, process-wide: out[0] mirrors started, out[1] mirrors refused (over the
+ * budget, or the allocation failed), out[2] path fetches (device calls), out[3] get_at calls
+ * answered from a fetched path, out[4] peak of the live mirror bytes. */
+const char* halp_mirror_stats(uint64_t out[5]);
+/* Zero the counts; the peak restarts from the bytes that are live now. */
+const char* halp_reset_mirror_stats(void);
 
 /* The prove core over device witness groups (Prover::commit_group x3 + finalize), with the
  * accumulation between the mix draw and the accum commit when accum_mode != 0:

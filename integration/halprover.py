@@ -37,6 +37,12 @@ def lib():
                                           C.POINTER(sz), vp]
         _lib.halp_set_deferred.restype = vp
         _lib.halp_set_deferred.argtypes = [C.c_int]
+        _lib.halp_set_mirror_budget.restype = vp
+        _lib.halp_set_mirror_budget.argtypes = [C.c_uint64]
+        _lib.halp_mirror_stats.restype = vp
+        _lib.halp_mirror_stats.argtypes = [C.POINTER(C.c_uint64)]
+        _lib.halp_reset_mirror_stats.restype = vp
+        _lib.halp_reset_mirror_stats.argtypes = []
         _lib.halp_last_profile.restype = vp
         _lib.halp_last_profile.argtypes = [C.c_char_p, sz]
     return _lib
@@ -74,6 +80,25 @@ def last_profile():
             k, v = kv.split("=")
             out[k] = out.get(k, 0.0) + float(v)
     return out
+
+
+DEFAULT_MIRROR_BUDGET = 4 << 30
+MIRROR_STATS = ("mirrors_started", "mirrors_refused", "path_fetches", "path_cache_hits", "peak_mirror_bytes")
+
+
+def set_mirror_budget(nbytes=DEFAULT_MIRROR_BUDGET):
+    """page-locked bytes the node heaps' host mirrors may hold at once, process-wide
+    (halp_set_mirror_budget); a heap over it is read with one path fetch per opening"""
+    _check(lib().halp_set_mirror_budget(int(nbytes)))
+
+
+def mirror_stats(reset=False):
+    """halp_mirror_stats as a dict keyed by MIRROR_STATS; reset: start the counts over after"""
+    out = (C.c_uint64 * 5)()
+    _check(lib().halp_mirror_stats(out))
+    if reset:
+        _check(lib().halp_reset_mirror_stats())
+    return dict(zip(MIRROR_STATS, (int(v) for v in out)))
 
 
 def prove_segment(hal, circuit, po2, code, data, accum, glob, accum_mode=0, work_cycles=0, bigint_records=None,

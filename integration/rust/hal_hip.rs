@@ -14,7 +14,11 @@
 //     (prove/merkle.rs:111-129); `get_at` on a Merkle node heap reads a page-locked host
 //     mirror of the heap, copied beside the next calls once hash_fold has built the root
 //     (r0hip_memcpy_d2h_start; a tree's ~50 x 17 node reads would otherwise be one synchronous
-//     copy each);
+//     copy each). The mirrors live under a budget (`with_mirror_budget`, 4 GiB by default; a
+//     heap is 256 * 2^po2 bytes and four are alive together): a heap that does not fit, or whose
+//     page-locked allocation fails, stays on the device only, and each opening's first `get_at`
+//     fetches its whole sibling path in one call (r0hip_merkle_paths_host), which the opening's
+//     following `get_at`s read from a per-allocation cache;
 //   * an allocation gets device memory at its first device use: `gather_sample` into a
 //     buffer that has none yet gathers straight to the host (r0hip_gather_sample_host) and
 //     `view` reads those words — MerkleTreeProver::prove's sample (merkle.rs:111-129) is only
@@ -27,7 +31,17 @@
 // driven over the same C symbols from Python, produces the golden seals:
 // tests/hal_prover.py + tests/test_gpu_parity.py::test_per_op_abi_prover_matches_golden_seal.
 
-use std::{cell::{Cell, RefCell}, ffi::CStr, marker::PhantomData, os::raw::c_void, rc::Rc, sync::OnceLock};
+use std::{
+    cell::{Cell, RefCell},
+    ffi::CStr,
+    marker::PhantomData,
+    os::raw::c_void,
+    rc::Rc,
+    sync::{
+        OnceLock,
+        atomic::{AtomicU64, Ordering},
+    },
+};
 
 use parking_lot::{ReentrantMutex, ReentrantMutexGuard};
 use risc0_core::{
@@ -65,6 +79,64 @@ fn device_ordinal() -> i32 {
 }
 
 // ---------------------------------------------------------------------------------------
+// Node-heap mirrors under a budget (the logic of integration/node_reads.h)
+
+/// Page-locked bytes the node heaps' host mirrors may hold at once, process-wide.
+pub const DEFAULT_MIRROR_BUDGET: u64 = 4 << 30;
+static MIRROR_BUDGET: AtomicU64 = AtomicU64::new(DEFAULT_MIRROR_BUDGET);
+static MIRROR_LIVE: AtomicU64 = AtomicU64::new(0);
+static MIRROR_PEAK: AtomicU64 = AtomicU64::new(0);
+/// mirrors started, mirrors refused, path fetches (device calls), path cache hits
+static MIRROR_COUNTS: [AtomicU64; 4] = [AtomicU64::new(0), AtomicU64::new(0), AtomicU64::new(0), AtomicU64::new(0)];
+
+/// A page-locked block of `bytes` for a mirror, or null when the live mirrors plus this one would
+/// pass the budget or the allocation fails: both are one refusal, never a panic.
+fn mirror_acquire(bytes: u64) -> *mut c_void {
+    let cap = MIRROR_BUDGET.load(Ordering::Relaxed);
+    let fits = MIRROR_LIVE.fetch_update(Ordering::Relaxed, Ordering::Relaxed, |cur| {
+        (bytes <= cap && cur <= cap - bytes).then(|| cur + bytes)
+    });
+    let Ok(before) = fits else {
+        MIRROR_COUNTS[1].fetch_add(1, Ordering::Relaxed);
+        return std::ptr::null_mut();
+    };
+    let mut h = std::ptr::null_mut();
+    let err = unsafe { r0hip_host_alloc(&mut h, bytes as usize) };
+    if !err.is_null() {
+        unsafe { r0hip_free_error(err) };
+        MIRROR_LIVE.fetch_sub(bytes, Ordering::Relaxed);
+        MIRROR_COUNTS[1].fetch_add(1, Ordering::Relaxed);
+        return std::ptr::null_mut();
+    }
+    MIRROR_PEAK.fetch_max(before + bytes, Ordering::Relaxed);
+    h
+}
+
+fn mirror_release(h: *mut c_void, bytes: u64) {
+    unsafe { r0hip_free_error(r0hip_host_free(h)) };
+    MIRROR_LIVE.fetch_sub(bytes, Ordering::Relaxed);
+}
+
+/// The nodes of the last opening fetched from an un-mirrored heap: node `j`, then the sibling
+/// `(j >> k) ^ 1` of each ancestor, k < levels (merkle.rs:131-138), 8 words each.
+#[derive(Default)]
+struct PathCache {
+    j: u64, // 0: empty
+    levels: usize,
+    words: Vec<u32>,
+}
+
+impl PathCache {
+    fn find(&self, node: u64) -> Option<&[u32]> {
+        if self.j == 0 {
+            return None;
+        }
+        let k = if node == self.j { 0 } else { (1..self.levels).find(|&k| node == (self.j >> k) ^ 1)? };
+        Some(&self.words[k * 8..k * 8 + 8])
+    }
+}
+
+// ---------------------------------------------------------------------------------------
 // Buffers
 
 /// A device allocation: bytes from r0hip_alloc, returned to libr0hip's pool on drop. The
@@ -85,6 +157,8 @@ struct DeviceAlloc {
     mirror: Cell<*mut c_void>,
     mirror_ok: Cell<bool>,
     pending: Cell<*mut c_void>,
+    /// a heap without a mirror: the last opening's nodes (`node`); cleared by every write
+    path: RefCell<PathCache>,
 }
 
 impl DeviceAlloc {
@@ -93,7 +167,7 @@ impl DeviceAlloc {
         tracker().lock().unwrap().alloc(bytes);
         Self { name, ptr: Cell::new(std::ptr::null_mut()), bytes, gathered: RefCell::new(None),
                mirror: Cell::new(std::ptr::null_mut()), mirror_ok: Cell::new(false),
-               pending: Cell::new(std::ptr::null_mut()) }
+               pending: Cell::new(std::ptr::null_mut()), path: RefCell::new(PathCache::default()) }
     }
 
     /// the device memory, allocated now if this is the first device use; words gathered to the
@@ -125,16 +199,19 @@ impl DeviceAlloc {
     fn written(&self) {
         self.settle();
         self.mirror_ok.set(false);
+        self.path.borrow_mut().j = 0;
     }
 
     /// hash_fold built the root: copy the heap to the host beside the next calls
     fn mirror_start(&self) {
         self.written();
         if self.mirror.get().is_null() {
-            let mut h = std::ptr::null_mut();
-            check(unsafe { r0hip_host_alloc(&mut h, self.bytes) });
-            self.mirror.set(h);
+            self.mirror.set(mirror_acquire(self.bytes as u64));
         }
+        if self.mirror.get().is_null() {
+            return; // over the budget, or no page-locked memory: get_at fetches paths (`node`)
+        }
+        MIRROR_COUNTS[0].fetch_add(1, Ordering::Relaxed);
         let mut c = std::ptr::null_mut();
         check(unsafe { r0hip_memcpy_d2h_start(self.mirror.get(), self.device(), self.bytes, &mut c) });
         self.pending.set(c);
@@ -146,16 +223,39 @@ impl DeviceAlloc {
         if !self.mirror_ok.get() {
             return None;
         }
-        let c = self.pending.get();
+        // finish releases the handle even when it fails: out of `pending` first (a panic in
+        // check() must not leave it for Drop's settle() to finish again), back only if not done
+        let c = self.pending.replace(std::ptr::null_mut());
         if !c.is_null() {
             let mut done = 0;
             check(unsafe { r0hip_copy_finish(c, 0, &mut done) });
             if done == 0 {
+                self.pending.set(c);
                 return None;
             }
-            self.pending.set(std::ptr::null_mut());
         }
         Some(self.mirror.get() as *const u8)
+    }
+
+    /// digest `node` (>= 2) of a node heap that has no mirror: from the last fetched path, else
+    /// one r0hip_merkle_paths_host call for `node` and every sibling above it, floor(log2 node)
+    /// digests (one for the root's children), which the opening's following get_ats hit
+    fn node(&self, node: u64) -> [u32; 8] {
+        let mut path = self.path.borrow_mut();
+        if let Some(w) = path.find(node) {
+            MIRROR_COUNTS[3].fetch_add(1, Ordering::Relaxed);
+            return w.try_into().unwrap();
+        }
+        path.j = 0;
+        let levels = ((63 - node.leading_zeros()) as usize).max(1);
+        path.words.resize(levels * 8, 0);
+        check(unsafe {
+            r0hip_merkle_paths_host(path.words.as_mut_ptr(), self.device() as *const u32, self.bytes / 32, &node, 1, levels)
+        });
+        MIRROR_COUNTS[2].fetch_add(1, Ordering::Relaxed);
+        path.j = node;
+        path.levels = levels;
+        path.words[..8].try_into().unwrap()
     }
 }
 
@@ -167,7 +267,7 @@ impl Drop for DeviceAlloc {
             unsafe { r0hip_free(self.ptr.get()) };
         }
         if !self.mirror.get().is_null() {
-            unsafe { r0hip_host_free(self.mirror.get()) };
+            mirror_release(self.mirror.get(), self.bytes as u64);
         }
     }
 }
@@ -262,6 +362,13 @@ impl<T: Clone> Buffer<T> for BufferImpl<T> {
         if let Some(h) = a.host() {
             let at = (self.offset + idx) * std::mem::size_of::<T>();
             return unsafe { std::ptr::read_unaligned(h.add(at) as *const T) };
+        }
+        // a digest below the root of a heap with no mirror (refused, not one in flight): the
+        // opening's path in one call. The root (node 1) has no path: one node either way.
+        let node = (self.offset + idx) as u64;
+        if std::mem::size_of::<T>() == 32 && !a.mirror_ok.get() && node >= 2 {
+            let w = a.node(node);
+            return unsafe { std::ptr::read_unaligned(w.as_ptr() as *const T) };
         }
         drop(a);
         self.read(idx, 1).pop().unwrap()
@@ -358,6 +465,24 @@ impl<HS: HipHash> HipHal<HS> {
     /// r0hip_recursion_witgen), r0hip_host_alloc / r0hip_host_free and r0hip_synchronize. A
     /// buffer shared with another thread is dropped only after that thread's queued work on it
     /// has been synchronised there.
+    /// The same HAL with the node heaps' host mirrors held to `bytes` of page-locked memory,
+    /// process-wide (DEFAULT_MIRROR_BUDGET, 4 GiB, unless set: every proof up to po2 21 mirrors
+    /// all its trees). A heap is 256 * 2^po2 bytes and the code, data, accum and check heaps are
+    /// alive together: ~1.07 GB pinned at po2 20, 4.3 GB at po2 22, 17 GB at po2 24. A heap that
+    /// does not fit, or cannot be allocated, costs one r0hip_merkle_paths_host call per opening
+    /// (~350 per proof) instead; 0 keeps every heap on the device only, as the CUDA HAL does.
+    pub fn with_mirror_budget(self, bytes: u64) -> Self {
+        MIRROR_BUDGET.store(bytes, Ordering::Relaxed);
+        self
+    }
+
+    /// Since the process started: (mirrors started, mirrors refused, path fetches, path cache
+    /// hits, peak live mirror bytes).
+    pub fn mirror_stats(&self) -> (u64, u64, u64, u64, u64) {
+        let c = |i: usize| MIRROR_COUNTS[i].load(Ordering::Relaxed);
+        (c(0), c(1), c(2), c(3), MIRROR_PEAK.load(Ordering::Relaxed))
+    }
+
     pub fn with_deferred(deferred: bool) -> Self {
         let _lock = device_lock().lock();
         check(unsafe { r0hip_init(device_ordinal()) });

@@ -225,6 +225,16 @@ unsafe extern "C" {
         -> *const c_char;
     pub fn r0hip_gather_sample_host(h_dst: *mut u32, d_src: *const u32, idx: usize, size: usize, stride: usize)
         -> *const c_char;
+    /// the nodes MerkleTreeProver::prove reads for each opening j = h_idx[i] (merkle.rs:108-140):
+    /// nodes[j], then nodes[(j >> k) ^ 1] for k < levels, straight to the host in one call
+    pub fn r0hip_merkle_paths_host(
+        h_dst: *mut u32,
+        d_nodes: *const u32,
+        heap_digests: usize,
+        h_idx: *const u64,
+        n: usize,
+        levels: usize,
+    ) -> *const c_char;
     pub fn r0hip_scatter(
         d_into: *mut u32,
         d_index: *const u32,

@@ -345,6 +345,33 @@ const char* r0hip_gather_sample_host(uint32_t* h_dst, const uint32_t* d_src, siz
     download(h_dst, d, size * 4);
   });
 }
+const char* r0hip_merkle_paths_host(uint32_t* h_dst, const uint32_t* d_nodes, size_t heap_digests,
+                                    const uint64_t* h_idx, size_t n, size_t levels) {
+  return wrap([&] {
+    if (!n) return;
+    R0_REQUIRE(levels >= 1 && levels < 64, "merkle_paths_host: levels = " + std::to_string(levels) +
+                                               " (an opening has the node itself and at most 62 siblings)");
+    R0_REQUIRE(h_dst && d_nodes && h_idx, "merkle_paths_host: null pointer");
+    // every index before any device work: the node and each sibling up to level levels-1 exist
+    for (size_t i = 0; i < n; i++) {
+      const uint64_t j = h_idx[i];
+      auto at = [&] { return "merkle_paths_host: index " + std::to_string(j) + " (h_idx[" + std::to_string(i) + "])"; };
+      R0_REQUIRE(j >= 1 && j < heap_digests, at() + " is outside [1, " + std::to_string(heap_digests) + ")");
+      R0_REQUIRE(levels == 1 || (j >> (levels - 1)) >= 2,
+                 at() + " has no sibling " + std::to_string(levels - 1) + " levels up (the root is node 1)");
+    }
+    const size_t words = n * levels * 8;
+    uint32_t* d = static_cast<uint32_t*>(scratch(words * 4, kSlotApiPaths));
+    const uint64_t* d_idx = nullptr;  // a single opening's index travels as a kernel argument
+    if (n > 1) {
+      uint64_t* di = static_cast<uint64_t*>(scratch(n * 8, kSlotApiPathIdx));
+      upload_async(di, h_idx, n * 8);
+      d_idx = di;
+    }
+    merkle_paths(stream(), d, d_nodes, heap_digests, d_idx, h_idx[0], n, levels);
+    download(h_dst, d, words * 4);
+  });
+}
 const char* r0hip_scatter(uint32_t* d_into, const uint32_t* d_index, const uint32_t* d_offsets,
                           const uint32_t* d_values, size_t cycles) {
   return wrap_dev([&] { scatter(stream(), d_into, d_index, d_offsets, d_values, cycles); });

@@ -1,6 +1,6 @@
 // Element-wise and polynomial HAL kernels for CDNA4: mix_poly_coeffs,
 // batch_evaluate_any, fri_fold, eltwise_{add,copy,zeroize,sum_extelem},
-// gather_sample, scatter, copy_elem_slice, prefix_products and the parallel
+// gather_sample, merkle_paths, scatter, copy_elem_slice, prefix_products and the parallel
 // synthetic division behind combos_divide. Semantics follow
 // risc0/zkp/src/hal/cpu.rs (line refs on each kernel). All HBM-bound except
 // evaluate_any/poly_divide, which are integer-VALU bound.
@@ -126,6 +126,21 @@ __global__ void fri_fold_kernel(uint32_t* out, const uint32_t* in, FpExt mix, ui
 __global__ void gather_kernel(uint32_t* dst, const uint32_t* src, uint64_t idx, uint64_t size, uint64_t stride) {
   uint64_t g = uint64_t(blockIdx.x) * kThreads + threadIdx.x;
   if (g < size) dst[g] = src[g * stride + idx];
+}
+// prove/merkle.rs:131-138: the nodes MerkleTreeProver::prove reads for one opening, one lane per
+// word. Word g is word g % 8 of path i = g / (8 * levels), level k: the node j itself at k = 0,
+// then the sibling (j >> k) ^ 1 of each ancestor. Eight lanes read one digest (32 contiguous
+// bytes) and the stores are contiguous. idx == nullptr: the one index `one` (a single opening
+// needs no upload). The launcher's caller validates every j; a node outside the heap stores 0.
+__global__ void merkle_paths_kernel(uint32_t* dst, const uint32_t* nodes, uint64_t heap_digests, const uint64_t* idx,
+                                    uint64_t one, uint64_t total, uint32_t levels) {
+  uint64_t g = uint64_t(blockIdx.x) * kThreads + threadIdx.x;
+  if (g >= total) return;
+  const uint64_t d = g >> 3;
+  const uint32_t k = uint32_t(d % levels);
+  const uint64_t j = idx ? idx[d / levels] : one;
+  const uint64_t node = k == 0 ? j : ((j >> k) ^ 1);
+  dst[g] = node < heap_digests ? nodes[node * 8 + (g & 7)] : 0u;
 }
 // cpu.rs:598-615: one lane per cycle walks its CSR slice
 // offsets at or past `limit` (the buffer's words) are skipped, and no row reads entries past
@@ -553,6 +568,15 @@ void gather_sample(hipStream_t s, uint32_t* dst, const uint32_t* src, size_t idx
   if (!size) return;
   hipLaunchKernelGGL(gather_kernel, dim3(div_up(size, kThreads)), dim3(kThreads), 0, s, dst, src, uint64_t(idx),
                      uint64_t(size), uint64_t(stride));
+  HIP_OK(hipGetLastError());
+}
+void merkle_paths(hipStream_t s, uint32_t* dst, const uint32_t* nodes, size_t heap_digests, const uint64_t* idx,
+                  uint64_t one, size_t n, size_t levels) {
+  if (!n || !levels) return;
+  R0_REQUIRE(levels < 64, "merkle_paths: levels out of range");
+  const uint64_t total = uint64_t(n) * levels * 8;
+  hipLaunchKernelGGL(merkle_paths_kernel, dim3(div_up(total, kThreads)), dim3(kThreads), 0, s, dst, nodes,
+                     uint64_t(heap_digests), idx, one, total, uint32_t(levels));
   HIP_OK(hipGetLastError());
 }
 void scatter(hipStream_t s, uint32_t* into, const uint32_t* index, const uint32_t* offsets, const uint32_t* values,

@@ -92,6 +92,8 @@ enum ScratchSlot : int {
   kSlotApiRem = 52,
   kSlotApiRems = 53,
   kSlotApiGather = 54,
+  kSlotApiPaths = 55,
+  kSlotApiPathIdx = 56,
   // accumulation (recursion_accum.hip, accum.hip, bigint.cpp)
   kSlotRecAccVals = 60,
   kSlotRecAccProds = 61,
@@ -345,6 +347,12 @@ void recursion_witgen(hipStream_t s, const uint32_t* ctrl, uint32_t* data, uint3
 void eltwise_sum_extelem(hipStream_t s, uint32_t* out, const uint32_t* in, size_t count, size_t to_add);
 void fri_fold(hipStream_t s, uint32_t* out, const uint32_t* in, FpExt mix, size_t count);
 void gather_sample(hipStream_t s, uint32_t* dst, const uint32_t* src, size_t idx, size_t size, size_t stride);
+// Merkle openings' sibling paths (prove/merkle.rs:131-138) out of a node heap of heap_digests
+// digests, root at 1: dst[(i*levels + k)*8 ..] = nodes[j] for k = 0, nodes[(j >> k) ^ 1] for
+// k >= 1, j = idx[i] (device array), or j = one for every i when idx is null. The caller has
+// checked every j; a node outside the heap is written as zeros, never read.
+void merkle_paths(hipStream_t s, uint32_t* dst, const uint32_t* nodes, size_t heap_digests, const uint64_t* idx,
+                  uint64_t one, size_t n, size_t levels);
 void mix_poly_coeffs(hipStream_t s, uint32_t* out, const uint32_t* in, const uint32_t* combos_dev,
                      const std::vector<uint32_t>& combos_host, FpExt mix_start, FpExt mix,
                      size_t input_size, size_t count);

@@ -86,6 +86,7 @@ def _declare(L):
         "r0hip_eltwise_copy_elem_slice": [vp, vp, sz, sz, sz, sz, sz, sz],
         "r0hip_gather_sample": [vp, vp, sz, sz, sz],
         "r0hip_gather_sample_host": [vp, vp, sz, sz, sz],
+        "r0hip_merkle_paths_host": [vp, vp, sz, vp, sz, sz],
         "r0hip_scatter": [vp, vp, vp, vp, sz],
         "r0hip_prefix_products": [vp, sz],
         "r0hip_hash_rows": [C.c_int, vp, vp, sz, sz],
@@ -341,6 +342,15 @@ class HipHal:
         """src[idx + i*stride], i < size, as a host array (r0hip_gather_sample_host)"""
         out = np.zeros(size, np.uint32)
         check(lib().r0hip_gather_sample_host(out.ctypes.data, src.ptr, idx, size, stride))
+        return out
+
+    def merkle_paths_host(self, nodes, idx, levels):
+        """the sibling paths of the openings at node indices idx of a node heap (root at 1), as
+        an (n, levels, 8) host array: [i, 0] = nodes[idx[i]], [i, k] = nodes[(idx[i] >> k) ^ 1]
+        (r0hip_merkle_paths_host; prove/merkle.rs:131-138)"""
+        j = np.ascontiguousarray(idx, dtype=np.uint64).reshape(-1)
+        out = np.zeros((j.size, max(int(levels), 0), 8), np.uint32)
+        check(lib().r0hip_merkle_paths_host(out.ctypes.data, nodes.ptr, nodes.size, j.ctypes.data, j.size, levels))
         return out
 
     def scatter(self, into, index, offsets, values):
