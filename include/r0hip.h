@@ -74,6 +74,25 @@ const char* r0hip_synchronize(void);
  *     that exits with work queued leaks its device blocks, stream and staging arena. */
 /* [host-only] */
 const char* r0hip_set_deferred(int on, int* was);
+/* Streams one proof of the calling host thread may use (thread-local, like the completion mode;
+ * 1 on every new thread, and the library's own pipeline, worker and verifier threads never
+ * change it). n = 1 is the single-stream launch sequence. With n >= 2 the code group's
+ * commitment (its NTTs, row hashes and tree layers) runs on a side stream: beside the witness
+ * generation in r0hip_prove_recursion and r0hip_prove_recursion_keyed, beside the data group's
+ * commitment in r0hip_prove_segment, _accum, _trace and _trace_resident. The roots enter the
+ * transcript in the same order and the seal is word for word that of n = 1. n is 1..3 (the
+ * thread's main stream and two side streams; with the process-wide copy stream these are the 4
+ * hardware queues HIP opens by default, no environment variable is needed; only one side stream
+ * has work today); any other n is an error that leaves the setting unchanged. *was (may be
+ * NULL) receives the previous value. The mode is for a caller that proves one task at a time
+ * (an r0vm GPU worker sees one proof's latency): alone, a proof leaves parts of the chip idle
+ * that a second stream can fill. r0hip_prove_segments, r0hip_prove_trace_segments and the
+ * worker already fill them with other segments and prove at n = 1 whatever the caller's
+ * setting. It costs no memory. Every call has joined its side streams when it returns, so the
+ * completion rules above are unchanged; the per-op calls are single ops and do not change.
+ * While r0hip_set_kernel_timing is on the thread behaves as n = 1. */
+/* [drains] */
+const char* r0hip_set_proof_streams(uint32_t n, uint32_t* was);
 /* The calling thread's entry-point calls so far, no device work: out[0] = [queues] and [drains]
  * calls made, out[1] = those that drained the stream before returning, out[2] = those that
  * returned with their work only queued. */

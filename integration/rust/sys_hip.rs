@@ -148,6 +148,8 @@ unsafe extern "C" {
     // its call counters {calls, drained, queued}
     pub fn r0hip_set_deferred(on: c_int, was: *mut c_int) -> *const c_char;
     pub fn r0hip_call_stats(out: *mut u64) -> *const c_char;
+    // streams one proof of the calling thread may use (1..3; for a worker proving one task at a time)
+    pub fn r0hip_set_proof_streams(n: u32, was: *mut u32) -> *const c_char;
     pub fn r0hip_free_error(err: *const c_char);
     // a device-to-host copy beside later calls (the HAL's node-heap mirrors, hal_hip.rs)
     pub fn r0hip_memcpy_d2h_start(h_dst: *mut c_void, d_src: *const c_void, bytes: usize,

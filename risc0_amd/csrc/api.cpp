@@ -33,7 +33,9 @@ void run_eval_check(const CircuitDef& c, uint32_t* check, const uint32_t* const*
 std::vector<uint32_t> prove_segment(const CircuitDef& c, int suite, uint32_t po2, const uint32_t* code,
                                     const uint32_t* data, const uint32_t* accum, uint32_t* global,
                                     bool write_version, uint32_t version, std::vector<uint32_t>* mix_out,
-                                    const UploadGate* uploads = nullptr, const AccumStep* acc = nullptr);
+                                    const UploadGate* uploads = nullptr, const AccumStep* acc = nullptr,
+                                    GroupWork* code_early = nullptr);
+GroupWork commit_group_side(int k, int suite, const uint32_t* witness, size_t cols, size_t po2);
 std::string last_profile();
 }  // namespace r0
 
@@ -152,6 +154,12 @@ const char* r0hip_set_deferred(int on, int* was) {
   return wrap_nosync([&] {
     if (was) *was = deferred_mode() ? 1 : 0;
     set_deferred_mode(on != 0);
+  });
+}
+const char* r0hip_set_proof_streams(uint32_t n, uint32_t* was) {
+  return wrap([&] {
+    if (was) *was = proof_streams();
+    set_proof_streams(n);
   });
 }
 const char* r0hip_call_stats(uint64_t* out) {
@@ -561,6 +569,12 @@ std::vector<uint32_t> prove_recursion(int suite, uint32_t po2, const uint32_t* d
   stage_reset();
   // WitnessGenerator::new (circuit/recursion/src/prove/witgen.rs:44-133)
   DevBuf data(data_cols * n), global(c->output_size), accum(accum_cols * n), noise(std::max(data_cols, accum_cols) * kZk);
+  // r0hip_set_proof_streams >= 2: the control group needs nothing of the witness generation, so
+  // its NTTs and hashes (throughput work) run on a side stream beside the generator, which is
+  // bound by the latency of its exec runs and waits for the host; prove_segment joins
+  GroupWork code_early;
+  const bool early = active_proof_streams() >= 2;
+  if (early) code_early = commit_group_side(1, suite, d_ctrl, c->group_size(1), po2);
   HIP_OK(hipMemsetD32Async(data.p, 0xFFFFFFFFu, data.words, s));
   HIP_OK(hipMemsetD32Async(global.p, 0xFFFFFFFFu, global.words, s));
   recursion_witgen(s, d_ctrl, data.p, global.p, n, h_wom, n_wom, h_cycles, n_cycles, h_iops, n_iops);
@@ -575,7 +589,8 @@ std::vector<uint32_t> prove_recursion(int suite, uint32_t po2, const uint32_t* d
   noise_fill(s, noise.p, accum_cols * kZk, 1);
   copy_elem_slice(s, accum.p, noise.p, accum_cols, kZk, 0, kZk, n - kZk, n);
   const AccumStep acc{accum.p, n_cycles};
-  return prove_segment(*c, suite, po2, d_ctrl, data.p, nullptr, global.p, false, 0, mix, nullptr, &acc);
+  return prove_segment(*c, suite, po2, d_ctrl, data.p, nullptr, global.p, false, 0, mix, nullptr, &acc,
+                       early ? &code_early : nullptr);
 }
 
 // The keyed noise of r0hip_prove_recursion_keyed: ChaCha20 under `key`, the data matrix with

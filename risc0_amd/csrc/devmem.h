@@ -42,4 +42,12 @@ struct DevBuf {
   ~DevBuf() { dev_free(p); }
 };
 
+// The device half of a register group's commitment (prover.cpp, commit_group_device):
+// coefficients, evaluations and the whole Merkle node heap, queued on some stream; nothing read
+// back yet.
+struct GroupWork {
+  DevBuf coeffs, evaluated, nodes;
+  size_t count = 0;
+};
+
 }  // namespace r0

@@ -37,7 +37,8 @@ namespace r0 {
 std::vector<uint32_t> prove_segment(const CircuitDef& c, int suite, uint32_t po2, const uint32_t* code,
                                     const uint32_t* data, const uint32_t* accum, uint32_t* global,
                                     bool write_version, uint32_t version, std::vector<uint32_t>* mix_out,
-                                    const UploadGate* uploads, const AccumStep* acc = nullptr);
+                                    const UploadGate* uploads, const AccumStep* acc = nullptr,
+                                    GroupWork* code_early = nullptr);
 // api.cpp: rv32im prove_core from a preflight trace, and the host check of an injector
 std::vector<uint32_t> prove_trace(int suite, uint32_t po2, uint32_t mode, const uint32_t* global_in,
                                   const uint32_t* inj_index, size_t inj_rows, const uint32_t* inj_offsets,
@@ -127,7 +128,14 @@ void run_provers(size_t k, F& prover) {
   }();
   std::vector<std::thread> threads;
   for (size_t t = caller ? 1 : 0; t < k; t++) threads.emplace_back(prover);
-  if (caller) prover();  // returns at its stop token; never throws (errors are per job)
+  if (caller) {
+    // the other provers fill the chip: the calling thread proves on one stream like them,
+    // whatever its r0hip_set_proof_streams setting, which it keeps
+    const uint32_t streams = proof_streams();
+    set_proof_streams(1);
+    prover();  // returns at its stop token; never throws (errors are per job)
+    set_proof_streams(streams);
+  }
   for (auto& t : threads) t.join();
 }
 

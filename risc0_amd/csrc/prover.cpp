@@ -145,6 +145,11 @@ struct PolyGroup {
     if (!bitrev) bit_reverse(stream(), coeffs.p, count, uint32_t(po2));
     tree.build(suite, evaluated.p, domain, count);
   }
+  // everything already queued (commit_group_device); the tree top is read here
+  PolyGroup(GroupWork w, size_t po2)
+      : coeffs(std::move(w.coeffs)), count(w.count), bitrev(coeffs_stay_bitrev(po2)), evaluated(std::move(w.evaluated)) {
+    tree.finish(std::move(w.nodes), evaluated.p, (size_t(1) << po2) * INV_RATE, count);
+  }
   // coefficients (natural order below po2 12), evaluations and leaf digests already made
   // chunk by chunk
   PolyGroup(int suite, DevBuf c, DevBuf ev, DevBuf leaf_nodes, size_t cnt, size_t po2)
@@ -212,6 +217,45 @@ std::vector<FpExt> map_pow(FpExt base, const uint32_t* exps, size_t n) {  // fie
 }
 
 }  // namespace
+
+namespace {
+GroupWork group_buffers(size_t cols, size_t po2) {
+  const size_t n = size_t(1) << po2, domain = n * INV_RATE;
+  GroupWork w;
+  w.count = cols;
+  w.coeffs = DevBuf(cols * n);
+  w.evaluated = DevBuf(cols * domain);
+  w.nodes = DevBuf(domain * 2 * 8);
+  return w;
+}
+void commit_group_queue(hipStream_t s, int suite, GroupWork& w, const uint32_t* witness, size_t po2) {
+  const size_t domain = (size_t(1) << po2) * INV_RATE;
+  ntt_interpolate_from(s, w.coeffs.p, witness, w.count, uint32_t(po2), true);
+  ntt_evaluate(s, w.evaluated.p, w.coeffs.p, w.count, uint32_t(po2 + 2), 2);
+  if (!coeffs_stay_bitrev(po2)) bit_reverse(s, w.coeffs.p, w.count, uint32_t(po2));
+  merkle_tree(s, suite, w.nodes.p, w.evaluated.p, domain, w.count);
+}
+}  // namespace
+
+// commit_group's device half on stream s: interpolate (zk shift fused), evaluate on the 4x
+// domain, row hashes and tree layers, the kernels of commit_group in its order. Nothing is
+// read back: PolyGroup(GroupWork, po2) reads the tree top.
+GroupWork commit_group_device(hipStream_t s, int suite, const uint32_t* witness, size_t cols, size_t po2) {
+  GroupWork w = group_buffers(cols, po2);
+  commit_group_queue(s, suite, w, witness, po2);
+  return w;
+}
+// The same on side stream k (r0hip_set_proof_streams >= 2), beside what the caller queues on the
+// main stream next. The buffers are taken first and the fork comes after, so the side stream
+// runs after every earlier use of those blocks and of `witness` on the main stream. The caller
+// joins k before anything reads the group (runtime.h: every function that forks has joined
+// before it returns; after a throw in between, drain_after_error waits for the side stream).
+GroupWork commit_group_side(int k, int suite, const uint32_t* witness, size_t cols, size_t po2) {
+  GroupWork w = group_buffers(cols, po2);
+  fork(k);
+  commit_group_queue(side_stream(k), suite, w, witness, po2);
+  return w;
+}
 
 // eval_check for one circuit (rv32im/src/prove/hal/cpu.rs:145-207 semantics)
 void run_eval_check(const CircuitDef& c, uint32_t* check, const uint32_t* const* groups, const uint32_t* mix,
@@ -347,6 +391,13 @@ struct Prover {
       ntt_interpolate_from(stream(), coeffs.p, witness, gs, uint32_t(po2), true);
     }
     groups[g].reset(new PolyGroup(suite, std::move(coeffs), gs, po2));
+    groups[g]->tree.commit(iop);
+  }
+  // commit_group's transcript half for a group whose device half is queued and joined: the
+  // tree top is read, then written and hashed into the transcript
+  void commit_group_finish(size_t g, GroupWork w) {
+    Span span("commit_group");
+    groups[g].reset(new PolyGroup(std::move(w), po2));
     groups[g]->tree.commit(iop);
   }
 
@@ -594,7 +645,7 @@ std::string last_profile() { return g_last_profile; }
 std::vector<uint32_t> prove_segment(const CircuitDef& c, int suite, uint32_t po2, const uint32_t* code,
                                     const uint32_t* data, const uint32_t* accum, uint32_t* global,
                                     bool write_version, uint32_t version, std::vector<uint32_t>* mix_out,
-                                    const UploadGate* uploads, const AccumStep* acc) {
+                                    const UploadGate* uploads, const AccumStep* acc, GroupWork* code_early) {
   R0_REQUIRE(suite >= 0 && suite <= 2, "unknown hash suite");
   R0_REQUIRE(!acc || (acc->accum && !accum), "prove_segment: give the accum group or an accumulation, not both");
   R0_REQUIRE(po2 >= 2 && po2 <= 24, "po2 out of range");
@@ -635,10 +686,25 @@ std::vector<uint32_t> prove_segment(const CircuitDef& c, int suite, uint32_t po2
       p.commit_group(g, w);
     }
   };
-  commit(1, 0, code);
-  prof.mark("commit_code");
-  commit(2, 1, data);
-  prof.mark("commit_data");
+  // r0hip_set_proof_streams >= 2 (never with a group still uploading): the code group's device
+  // work runs on side stream 1, started by the caller before its witness generation
+  // (code_early) or here, beside the data group's on the main stream. The roots are read and
+  // hashed into the transcript in the reference's order, code then data, and the side stream is
+  // joined before anything reads the code group's buffers.
+  if (code_early || (!uploads && active_proof_streams() >= 2)) {
+    GroupWork cw = code_early ? std::move(*code_early) : commit_group_side(1, suite, code, c.group_size(1), po2);
+    GroupWork dw = commit_group_device(s, suite, data, c.group_size(2), po2);
+    join(1);
+    p.commit_group_finish(1, std::move(cw));
+    prof.mark("commit_code");
+    p.commit_group_finish(2, std::move(dw));
+    prof.mark("commit_data");
+  } else {
+    commit(1, 0, code);
+    prof.mark("commit_code");
+    commit(2, 1, data);
+    prof.mark("commit_data");
+  }
   std::vector<uint32_t> mix(c.mix_size);
   for (auto& m : mix) m = p.iop.rng->random_elem();
   if (mix_out) *mix_out = mix;

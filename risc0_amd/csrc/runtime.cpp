@@ -64,6 +64,11 @@ struct ThreadCtx {
   // inside an entry point that will return without draining (call_will_queue .. call_queued)
   bool queueing = false;
   hipEvent_t order_ev = nullptr;  // order_after_thread_work's, recorded again at each use
+  // r0hip_set_proof_streams: the setting, the side streams (created on first use) and the events
+  // that order work across the thread's streams; idle whenever the main stream is drained
+  uint32_t proof_streams = 1;
+  hipStream_t side[kMaxProofStreams - 1] = {};
+  hipEvent_t sync_ev = nullptr;  // order_stream_after's, recorded again at each use
   uint64_t calls = 0, calls_drained = 0, calls_queued = 0;  // r0hip_call_stats
   // the idle pool and scratch blocks to the shared lists (caller holds g_mu; stream drained)
   void hand_back_memory() {
@@ -89,6 +94,9 @@ struct ThreadCtx {
     std::lock_guard<std::mutex> lk(g_mu);
     hand_back_memory();
     g_free_streams.push_back(stream);
+    for (hipStream_t ss : side)
+      if (ss) g_free_streams.push_back(ss);  // joined before the last call returned
+    if (sync_ev) g_free_events.push_back(sync_ev);
     if (stage.base) g_free_stages.push_back(Stage{stage.base, stage.cap, 0});
     if (order_ev) g_free_events.push_back(order_ev);
     // superseded arenas in stage_old are left allocated (rare: only after growth)
@@ -199,6 +207,9 @@ void stream_drained() noexcept {
 void drain_after_error() noexcept {
   if (!t_ctx.stream) return;
   (void)hipStreamSynchronize(t_ctx.stream);
+  // a throw between a fork and its join leaves side-stream work the main stream never waited for
+  for (hipStream_t ss : t_ctx.side)
+    if (ss) (void)hipStreamSynchronize(ss);
   stream_drained();
 }
 
@@ -258,6 +269,60 @@ void order_after_thread_work(hipStream_t other) {
   HIP_OK(hipEventRecord(t_ctx.order_ev, t_ctx.stream));
   HIP_OK(hipStreamWaitEvent(other, t_ctx.order_ev, 0));
 }
+
+// ---- several streams for one proof ---------------------------------------------
+namespace {
+bool g_kt_on = false;  // kernel timing (ktimer_enable)
+
+hipEvent_t cached_event() {
+  hipEvent_t ev = nullptr;
+  {
+    std::lock_guard<std::mutex> lk(g_mu);
+    if (!g_free_events.empty()) {
+      ev = g_free_events.back();
+      g_free_events.pop_back();
+    }
+  }
+  if (!ev) HIP_OK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+  return ev;
+}
+}  // namespace
+
+uint32_t proof_streams() noexcept { return t_ctx.proof_streams; }
+
+void set_proof_streams(uint32_t n) {
+  R0_REQUIRE(n >= 1 && n <= kMaxProofStreams,
+             "proof streams must be 1.." + std::to_string(kMaxProofStreams) + ", got " + std::to_string(n));
+  t_ctx.proof_streams = n;
+}
+
+uint32_t active_proof_streams() noexcept { return g_kt_on ? 1 : t_ctx.proof_streams; }
+
+hipStream_t side_stream(int k) {
+  ensure_init();
+  R0_REQUIRE(k >= 1 && k < int(kMaxProofStreams), "no such side stream");
+  hipStream_t& ss = t_ctx.side[k - 1];
+  if (!ss) {
+    std::lock_guard<std::mutex> lk(g_mu);
+    if (!g_free_streams.empty()) {
+      ss = g_free_streams.back();
+      g_free_streams.pop_back();
+    }
+  }
+  if (!ss) HIP_OK(hipStreamCreateWithFlags(&ss, hipStreamNonBlocking));
+  return ss;
+}
+
+void order_stream_after(hipStream_t waiter, hipStream_t on) {
+  if (waiter == on) return;
+  if (!t_ctx.sync_ev) t_ctx.sync_ev = cached_event();
+  // the wait is queued before this returns, so the event is free for the next record
+  HIP_OK(hipEventRecord(t_ctx.sync_ev, on));
+  HIP_OK(hipStreamWaitEvent(waiter, t_ctx.sync_ev, 0));
+}
+
+void fork(int k) { order_stream_after(side_stream(k), stream()); }
+void join(int k) { order_stream_after(stream(), side_stream(k)); }
 
 const uint32_t* dev_table(const std::string& key, const std::function<std::vector<uint32_t>()>& gen) {
   ensure_init();
@@ -425,7 +490,6 @@ struct KRec {
   double bytes, mm;
   hipEvent_t a, b;
 };
-bool g_kt_on = false;
 std::vector<KRec> g_kt;
 }  // namespace
 

@@ -70,8 +70,7 @@ enum ScratchSlot : int {
   kSlotEcMatExt = 24,
   kSlotEcPolyMixNb = 25,
   kSlotEcColPtr = 26,
-  kSlotEcUniform = 27,
-  // prover uploads (prover.cpp): evaluation points per group (3 groups), check points,
+  kSlotEcUniform = 27,  // prover uploads (prover.cpp): evaluation points per group (3 groups), check points,
   // mix_poly_coeffs row lists, combos deltas, query gather tables
   kSlotTapXs = 33,  // .. 35
   kSlotCheckXs = 37,
@@ -170,6 +169,30 @@ void call_stats(uint64_t out[3]) noexcept;  // this thread's calls: all, drained
 // Make stream `other` wait for the work this thread has queued so far (an event on the thread's
 // stream); nothing to do when the thread's last call drained.
 void order_after_thread_work(hipStream_t other);
+
+// One proof's independent work on several streams (r0hip_set_proof_streams; 1 on every new
+// thread, which is the single-stream launch sequence with no extra HIP call). With n >= 2 a
+// function may move independent work to one of the thread's side streams, created on first use
+// and handed over or leaked with the main stream when the thread exits. Invariant: every
+// function that forks has joined before it returns (the main stream waits for the side stream),
+// so "main stream drained" still means "all of this thread's work is done", and
+// release_thread_memory, download, the deferred-mode rules and order_after_thread_work hold
+// unchanged. Buffers used on a side stream are requested before the fork and released after the
+// join. After an error drain_after_error also waits for the side streams: an exception between
+// a fork and its join hands no block back while side kernels run.
+constexpr uint32_t kMaxProofStreams = 3;  // main + 2 side streams; with the copy stream, HIP's 4 queues
+uint32_t proof_streams() noexcept;        // the thread's setting
+void set_proof_streams(uint32_t n);       // 1..kMaxProofStreams, the caller has drained
+// The setting in effect: 1 while kernel timing is on (KScope and Profile bracket work with events
+// on the main stream, which must keep covering it).
+uint32_t active_proof_streams() noexcept;
+hipStream_t side_stream(int k);  // k = 1, 2
+// `waiter` runs what is queued on it from now on after everything queued on `on` so far (one
+// event record and one wait); fork(k) orders side stream k after the main stream, join(k) the
+// main stream after side stream k.
+void order_stream_after(hipStream_t waiter, hipStream_t on);
+void fork(int k);
+void join(int k);
 
 // Stream-ordered host->device upload through a pinned bump arena, so the caller's
 // host data may die immediately. The arena is recycled by stage_reset() (call only

@@ -68,6 +68,7 @@ def _declare(L):
         "r0hip_poly_ext": [C.c_char_p, u32p, u32p, u32p, u32p, u32p],
         "r0hip_synchronize": [],
         "r0hip_set_deferred": [C.c_int, C.POINTER(C.c_int)],
+        "r0hip_set_proof_streams": [C.c_uint32, C.POINTER(C.c_uint32)],
         "r0hip_call_stats": [C.POINTER(C.c_uint64)],
         "r0hip_batch_expand_into_evaluate_ntt": [vp, vp, sz, C.c_uint32, C.c_uint32],
         "r0hip_batch_interpolate_ntt": [vp, sz, C.c_uint32],
@@ -228,6 +229,19 @@ class HipHal:
             yield self
         finally:
             self.set_deferred(was)
+
+    # ---- streams one proof of the calling thread may use (r0hip_set_proof_streams) ----
+    def set_proof_streams(self, n):
+        return set_proof_streams(n)
+
+    @contextlib.contextmanager
+    def proof_streams(self, n):
+        """`with hal.proof_streams(2):` the setting for a block of calls, restored after it"""
+        was = set_proof_streams(n)
+        try:
+            yield self
+        finally:
+            set_proof_streams(was)
 
     # ---- allocation (hal/mod.rs:67-100) ----
     def alloc_elem(self, name, size):
@@ -1043,6 +1057,17 @@ def call_stats():
     out = (C.c_uint64 * 3)()
     check(lib().r0hip_call_stats(out))
     return {"calls": int(out[0]), "drained": int(out[1]), "queued": int(out[2])}
+
+
+def set_proof_streams(n):
+    """r0hip_set_proof_streams: how many streams one proof of the calling thread may use (1, the
+    default, to 3). With n >= 2 the code group's commitment runs on a side stream, beside the
+    witness generation (prove_recursion*) or the data group's commitment; the seal is the same
+    words. For a caller that proves one task at a time; a pipeline or a worker fills the chip
+    with other segments and runs at 1. Returns the previous value."""
+    was = C.c_uint32(0)
+    check(lib().r0hip_set_proof_streams(C.c_uint32(n), C.byref(was)))
+    return int(was.value)
 
 
 def mem_stats():
