@@ -387,6 +387,50 @@ const char* r0hip_prove_segment_trace(int suite, uint32_t po2, uint32_t mode, co
                                       const r0hip_bigint_back* h_bigint, size_t n_bigint, uint32_t* h_seal,
                                       size_t seal_cap, size_t* seal_len, uint32_t* h_mix_out);
 
+/* ---- the injector in its compact form: the preflight's Back records ----
+ * build_injector (circuit/rv32im/src/prove/witgen/mod.rs:226-270) expands, row by row, the row's
+ * Back (witgen/preflight.rs:47-57) and Injector::set_cycle (mod.rs:353-365) into the (offset,
+ * value) list hal.scatter takes. Here the caller hands over what the expansion reads,
+ * trace.backs and trace.cycles, and the expansion runs on the device. One record per row whose
+ * Back is not None; its payload is the reference's own array, PLAIN u32 words: the device does
+ * what Injector::set does, Val::from(u32) = encode(x % P) (core/src/field/baby_bear.rs:202-204).
+ * The payload's word k goes to column k of the kind's column list (Poseidon2State::offsets,
+ * Sha2State::fp_offsets, BigIntState::offsets; ECALL_S0..S2); a SHA-2 record's last three words
+ * (a, e, w; Sha2State::u32_array) go out as Injector::set_u32_bits writes them, bit i of word k
+ * in column u32_offsets[k] + i. */
+#define R0HIP_BACK_ECALL     1  /*  3 words: s0, s1, s2                      (mod.rs:240-247) */
+#define R0HIP_BACK_POSEIDON2 2  /* 39 words: Poseidon2State::as_array        (witgen/poseidon2.rs:136-179) */
+#define R0HIP_BACK_SHA2      3  /* 10 words: Sha2State::fp_array (7), a, e, w (witgen/sha2.rs:45-59) */
+#define R0HIP_BACK_BIGINT    4  /* 22 words: BigIntState::as_array           (witgen/bigint.rs:213-238) */
+typedef struct r0hip_back { uint32_t row; uint32_t kind; uint32_t word; } r0hip_back; /* word: index of the payload's first word */
+typedef struct r0hip_backs {
+  const r0hip_back* recs; size_t n;        /* rows strictly increasing; Back::None rows have no record */
+  const uint32_t* words;  size_t n_words;  /* payloads, PLAIN u32 as the reference's arrays hold them */
+  size_t inj_rows;                         /* rows that get the set_cycle columns (trace.cycles.len()), <= 2^po2 */
+} r0hip_backs;
+/* build_injector plus hal.scatter in front of r0hip_rv32im_witgen: writes into d_data (211
+ * columns x rows, column-major, every word INVALID or as r0hip_prove_segment_trace's fill leaves
+ * it) the words the scatter of build_injector's output writes: for every row r < inj_rows the
+ * five set_cycle columns from r and h_cycles[r].{pc, state, machine_mode} (h_cycles: inj_rows
+ * RawPreflightCycle records, host), and every record's payload in its kind's columns. No other
+ * word is touched. The struct and its arrays are on the host and are consumed before the call
+ * returns. Checked on the host before any launch, in O(n), the message naming the record: recs /
+ * words NULL with a nonzero count, rows not strictly increasing or >= inj_rows, inj_rows > rows,
+ * a kind outside 1..4, a payload that ends past n_words. */
+/* [queues] */
+const char* r0hip_rv32im_inject_backs(uint32_t* d_data, size_t rows, const void* h_cycles, const r0hip_backs* backs);
+/* r0hip_prove_segment_trace from the Back records: the same sequence and the same seal, with the
+ * injector expanded on the device from `backs` (checked as above, against 2^po2 rows) and the
+ * accumulation's r0hip_bigint_back records derived on the host from the BigInt payloads (row,
+ * poly_op = word 3, coeff = word 4, bytes = the low 8 bits of words 5..20), in O(n). A record
+ * whose kind's columns are not ones its row's instruction arm takes from the injector is handled
+ * as the same entries of a CSR injector are: the outcome, a seal or the reference's error text,
+ * is that of r0hip_prove_segment_trace on the expanded list. */
+/* [drains] */
+const char* r0hip_prove_segment_trace_backs(int suite, uint32_t po2, uint32_t mode, const uint32_t* h_global,
+                                            const r0hip_raw_preflight_trace* preflight, const r0hip_backs* backs,
+                                            uint32_t* h_seal, size_t seal_cap, size_t* seal_len, uint32_t* h_mix_out);
+
 /* The same with every input already resident in device memory (the global vector, the
  * injector arrays, and d_preflight's cycles / txns / bigint_bytes are DEVICE pointers; the
  * struct itself and h_bigint are on the host): what the benchmark times, inputs in HBM.
@@ -550,7 +594,13 @@ const char* r0hip_prove_trace_segments(int suite, uint32_t po2, r0hip_trace_job*
  * host memory (staged by the uploader) and are proved as r0hip_prove_recursion_keyed proves
  * them with the worker's key and stream_id = the job's ticket, so the seal equals that call's on
  * the same inputs. A job's own failure goes to job->error (malloc'd, free() it) and the other
- * jobs continue. With verify, every seal goes through r0hip_verify_seal (recursion: against the
+ * jobs continue. Jobs of kind R0HIP_JOB_RV32IM_BACKS are rv32im jobs whose injector is job->backs
+ * (r0hip_backs above) instead of the CSR arrays: they use trace.mode, trace.h_global and
+ * trace.preflight, ignore trace.h_inj_* / inj_rows and h_bigint / n_bigint (the BigInt records
+ * are derived from the payloads), stage only the records and the payload words, and give the
+ * seal of r0hip_prove_segment_trace_backs. Their records are checked in r0hip_worker_submit, as
+ * r0hip_rv32im_inject_backs checks them; the r0hip_backs struct stays valid like the arrays.
+ * With verify, every seal goes through r0hip_verify_seal (recursion: against the
  * job's h_code_roots allow-list); a failed check sets "receipt verification failed: ..." on
  * that job alone.
  * r0hip_worker_wait returns the next finished job in completion order, each job exactly once.
@@ -563,6 +613,7 @@ const char* r0hip_prove_trace_segments(int suite, uint32_t po2, r0hip_trace_job*
 typedef struct r0hip_worker r0hip_worker;
 #define R0HIP_JOB_RV32IM_TRACE 0
 #define R0HIP_JOB_RECURSION 1
+#define R0HIP_JOB_RV32IM_BACKS 2
 typedef struct r0hip_recursion_input {
   const uint32_t* h_ctrl;        /* control group, 23 columns x 2^po2, host */
   const uint32_t* h_wom;         /* as r0hip_recursion_witgen takes them */
@@ -578,7 +629,7 @@ typedef struct r0hip_worker_job {
   uint32_t kind;                      /* R0HIP_JOB_* */
   int suite;
   uint32_t po2;
-  r0hip_trace_input trace;            /* kind 0 */
+  r0hip_trace_input trace;            /* kind 0; kind 2: mode, h_global and preflight */
   const r0hip_bigint_back* h_bigint;  /* kind 0: the trace's BigInt backs (NULL, 0 if none) */
   size_t n_bigint;
   r0hip_recursion_input recursion;    /* kind 1 */
@@ -593,6 +644,7 @@ typedef struct r0hip_worker_job {
   double prove_ms;                    /* out: host milliseconds from a prover taking the job to its
                                          seal in host memory (the wait for its upload included) */
   uint64_t ticket;                    /* out: submission number, from 0 */
+  const r0hip_backs* backs;           /* kind 2: the Back records (read for no other kind) */
 } r0hip_worker_job;
 /* [drains] */
 const char* r0hip_worker_create(r0hip_worker** out, uint32_t max_po2, uint32_t in_flight, int verify,

@@ -12,6 +12,13 @@
 // at tableSplitCycle, the same RawExecBuffers / RawPreflightTrace the CUDA HAL passes) and the
 // recursion circuit's (r0hip_recursion_witgen).
 //
+// The injector in front of the rv32im witgen need not be built on the host: with the data
+// group all INVALID, r0hip_rv32im_inject_backs(data, rows, trace.cycles, &R0HipBacks) writes what
+// build_injector + hal.scatter (witgen/mod.rs:146-162, 226-270) write, from trace.backs packed
+// as records and plain payload words ("From the preflight's Back records").
+// WitnessGenerator::hal_generate_witness calls it where it scatters today; the CircuitHal
+// traits, which are handed the scattered group, do not change.
+//
 // Selection (one arm each):
 //   circuit/rv32im/src/prove/mod.rs:45-55       if #[cfg(feature = "hip")] { self::hal::hip::segment_prover() }
 //   circuit/recursion/src/prove/mod.rs:82-93    if #[cfg(feature = "hip")] { self::hal::hip::recursion_prover(hashfn) }

@@ -90,6 +90,33 @@ pub struct R0HipWorker {
 /// Job kinds of R0HipWorkerJob (R0HIP_JOB_*).
 pub const R0HIP_JOB_RV32IM_TRACE: u32 = 0;
 pub const R0HIP_JOB_RECURSION: u32 = 1;
+pub const R0HIP_JOB_RV32IM_BACKS: u32 = 2;
+
+/// Record kinds of R0HipBack (R0HIP_BACK_*) and their payload sizes in words.
+pub const R0HIP_BACK_ECALL: u32 = 1; // 3: s0, s1, s2
+pub const R0HIP_BACK_POSEIDON2: u32 = 2; // 39: Poseidon2State::as_array
+pub const R0HIP_BACK_SHA2: u32 = 3; // 10: Sha2State::fp_array, then a, e, w
+pub const R0HIP_BACK_BIGINT: u32 = 4; // 22: BigIntState::as_array
+
+/// One row's Back record (struct r0hip_back): `word` is the index of its payload's first word.
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct R0HipBack {
+    pub row: u32,
+    pub kind: u32,
+    pub word: u32,
+}
+
+/// The injector as the preflight's Back records (struct r0hip_backs): what build_injector reads,
+/// not what it writes. Payload words are plain u32, as the reference's arrays hold them.
+#[repr(C)]
+pub struct R0HipBacks {
+    pub recs: *const R0HipBack,
+    pub n: usize,
+    pub words: *const u32,
+    pub n_words: usize,
+    pub inj_rows: usize,
+}
 
 /// One recursion job's host arrays (struct r0hip_recursion_input): the control group and the
 /// preflight as r0hip_recursion_witgen takes them, and the allow-list of its receipt check.
@@ -107,7 +134,8 @@ pub struct R0HipRecursionInput {
 }
 
 /// One job of the GPU worker (struct r0hip_worker_job): an rv32im prove_core from a preflight
-/// trace (kind 0) or a recursion proof (kind 1). It must not move, and its host arrays must
+/// trace (kind 0), the same from its Back records (kind 2, `backs`) or a recursion proof (kind
+/// 1). It must not move, and its host arrays must
 /// stay valid, from r0hip_worker_submit until r0hip_worker_wait hands it back.
 #[repr(C)]
 pub struct R0HipWorkerJob {
@@ -128,6 +156,7 @@ pub struct R0HipWorkerJob {
     pub verify_ms: f64,
     pub prove_ms: f64,
     pub ticket: u64,
+    pub backs: *const R0HipBacks,
 }
 
 #[link(name = "r0hip")]
@@ -367,6 +396,26 @@ unsafe extern "C" {
         preflight: *const c_void,
         h_bigint: *const R0HipBigIntBack,
         n_bigint: usize,
+        h_seal: *mut u32,
+        seal_cap: usize,
+        seal_len: *mut usize,
+        h_mix_out: *mut u32,
+    ) -> *const c_char;
+    /// build_injector plus hal.scatter from the Back records, in front of r0hip_rv32im_witgen
+    pub fn r0hip_rv32im_inject_backs(
+        d_data: *mut u32,
+        rows: usize,
+        h_cycles: *const c_void,
+        backs: *const R0HipBacks,
+    ) -> *const c_char;
+    /// r0hip_prove_segment_trace from the Back records: no injector arrays, no BigInt records
+    pub fn r0hip_prove_segment_trace_backs(
+        suite: c_int,
+        po2: u32,
+        mode: u32,
+        h_global: *const u32,
+        preflight: *const c_void,
+        backs: *const R0HipBacks,
         h_seal: *mut u32,
         seal_cap: usize,
         seal_len: *mut usize,

@@ -19,6 +19,7 @@
 #include <stdexcept>
 #include <vector>
 
+#include "backs.h"
 #include "circuit.h"
 #include "devmem.h"
 #include "runtime.h"
@@ -457,6 +458,50 @@ namespace r0 {
 void check_injector(const uint32_t* index, size_t rows, const uint32_t* offsets, const uint32_t* values,
                     size_t limit, size_t seg_rows);
 
+// r0hip_backs on the host (backs.h)
+BacksInfo check_backs(const r0hip_backs* b, size_t seg_rows, const std::string& who) {
+  R0_REQUIRE(b, who + ": backs is NULL");
+  R0_REQUIRE(b->inj_rows <= seg_rows, who + ": backs: inj_rows " + std::to_string(b->inj_rows) + " above the segment's " +
+                                          std::to_string(seg_rows) + " rows");
+  R0_REQUIRE(b->n == 0 || b->recs, who + ": backs: recs is NULL with " + std::to_string(b->n) + " records");
+  R0_REQUIRE(b->n_words == 0 || b->words, who + ": backs: words is NULL with n_words " + std::to_string(b->n_words));
+  R0_REQUIRE(b->n_words < (size_t(1) << 32), who + ": backs: n_words does not fit a record's 32-bit word index");
+  const rvwg::BackTables& T = rv32im_witgen_back_tables();
+  BacksInfo info;
+  for (size_t k = 0; k < b->n; k++) {
+    const r0hip_back& r = b->recs[k];
+    auto rec = [&] { return who + ": backs: record " + std::to_string(k) + " (row " + std::to_string(r.row) + ")"; };
+    R0_REQUIRE(r.row < b->inj_rows, rec() + ": row at or past inj_rows " + std::to_string(b->inj_rows));
+    R0_REQUIRE(k == 0 || r.row > b->recs[k - 1].row,
+               rec() + ": rows must strictly increase (the record before it has row " +
+                   std::to_string(k ? b->recs[k - 1].row : 0) + ")");
+    R0_REQUIRE(r.kind >= 1 && r.kind < rvwg::kBackKinds, rec() + ": kind " + std::to_string(r.kind) + " is not 1..4");
+    const size_t size = size_t(T.plain[r.kind]) + T.bits[r.kind];
+    R0_REQUIRE(size_t(r.word) + size <= b->n_words, rec() + ": payload words [" + std::to_string(r.word) + ", " +
+                                                        std::to_string(size_t(r.word) + size) + ") end past n_words " +
+                                                        std::to_string(b->n_words));
+    info.entries += size_t(T.plain[r.kind]) + 32 * size_t(T.bits[r.kind]);
+    info.n_bigint += r.kind == R0HIP_BACK_BIGINT;
+  }
+  return info;
+}
+
+std::vector<r0hip_bigint_back> backs_bigint_records(const r0hip_backs& b, size_t n_bigint) {
+  std::vector<r0hip_bigint_back> out;
+  out.reserve(n_bigint);
+  for (size_t k = 0; k < b.n && n_bigint; k++) {
+    if (b.recs[k].kind != R0HIP_BACK_BIGINT) continue;
+    const uint32_t* w = b.words + b.recs[k].word;  // is_ecall, mode, pc, poly_op, coeff, bytes[16], next_state
+    r0hip_bigint_back r{};
+    r.row = b.recs[k].row;
+    r.poly_op = w[3];
+    r.coeff = w[4];
+    for (int i = 0; i < 16; i++) r.bytes[i] = uint8_t(w[5 + i]);
+    out.push_back(r);
+  }
+  return out;
+}
+
 // SegmentProverImpl::prove_core from a preflight (circuit/rv32im/src/prove/hal/mod.rs:143-224):
 // WitnessGenerator::hal_generate_witness (witgen/mod.rs:135-176: globals, code and data
 // INVALID, the injector scattered into data, stepExec, zeroize), then the prove core with the
@@ -465,13 +510,17 @@ void check_injector(const uint32_t* index, size_t rows, const uint32_t* offsets,
 // inputs_ready (resident only): called with the stream after the groups' fill (which reads no
 // input) and before the first read of the inputs (the segment pipeline makes the stream wait for
 // their upload there, so the fill runs while the trace still uploads).
+// backs: the injector as checked Back records (backs.h) instead of the inj_* arrays, which are
+// then not read; its arrays are device pointers when `resident`.
 std::vector<uint32_t> prove_trace(int suite, uint32_t po2, uint32_t mode, const uint32_t* global_in,
                                   const uint32_t* inj_index, size_t inj_rows, const uint32_t* inj_offsets,
                                   const uint32_t* inj_values, const r0hip_raw_preflight_trace* pf,
                                   const r0hip_bigint_back* h_bigint, size_t n_bigint, bool resident,
-                                  std::vector<uint32_t>* mix, const std::function<void(hipStream_t)>& inputs_ready) {
+                                  std::vector<uint32_t>* mix, const std::function<void(hipStream_t)>& inputs_ready,
+                                  const TraceBacks* backs) {
   const CircuitDef* c = find_circuit("rv32im");
-  R0_REQUIRE(global_in && inj_index && pf && pf->cycles, "r0hip_prove_segment_trace: null argument");
+  if (backs) inj_rows = backs->inj_rows;
+  R0_REQUIRE(global_in && (inj_index || backs) && pf && pf->cycles, "r0hip_prove_segment_trace: null argument");
   R0_REQUIRE(po2 >= 2 && po2 <= 24, "r0hip_prove_segment_trace: po2 out of range");
   R0_REQUIRE(n_bigint == 0 || h_bigint, "r0hip_prove_segment_trace: h_bigint is NULL with n_bigint > 0");
   const size_t n = size_t(1) << po2;
@@ -485,6 +534,7 @@ std::vector<uint32_t> prove_trace(int suite, uint32_t po2, uint32_t mode, const 
   // nothing reads INVALID (rv32im_prover_groups_fill), then the injector (rv32im_prover_inject)
   rv32im_prover_groups_fill(s, data.p, code.p, accum.p, n, c->group_size(0));
   const uint32_t *idx = inj_index, *off = inj_offsets, *val = inj_values;
+  const uint32_t *recs = backs ? backs->recs : nullptr, *words = backs ? backs->words : nullptr;
   const rvwg::PreflightCycle* cyc = static_cast<const rvwg::PreflightCycle*>(pf->cycles);
   const rvwg::MemoryTxn* txn = static_cast<const rvwg::MemoryTxn*>(pf->txns);
   const uint8_t* big = pf->bigint_bytes;
@@ -494,16 +544,24 @@ std::vector<uint32_t> prove_trace(int suite, uint32_t po2, uint32_t mode, const 
   } else {
     R0_REQUIRE((pf->txns_len == 0 || pf->txns) && (pf->bigint_bytes_len == 0 || pf->bigint_bytes),
                "r0hip_prove_segment_trace: null trace array with a nonzero count");
-    check_injector(inj_index, inj_rows, inj_offsets, inj_values, data_cols * n, n);
-    const size_t n_inj = inj_index[inj_rows];
     upload_async(global.p, global_in, global.words * 4);
-    auto* d_idx = static_cast<uint32_t*>(scratch((inj_rows + 1) * 4, kSlotRvInjIndex));
-    auto* d_off = static_cast<uint32_t*>(scratch(n_inj * 4 + 4, kSlotRvInjOffsets));
-    auto* d_val = static_cast<uint32_t*>(scratch(n_inj * 4 + 4, kSlotRvInjValues));
-    upload_async(d_idx, inj_index, (inj_rows + 1) * 4);
-    upload_async(d_off, inj_offsets, n_inj * 4);
-    upload_async(d_val, inj_values, n_inj * 4);
-    idx = d_idx, off = d_off, val = d_val;
+    if (backs) {  // checked by the caller (check_backs)
+      auto* d_recs = static_cast<uint32_t*>(scratch(backs->n * 12 + 4, kSlotRvBackRecs));
+      auto* d_words = static_cast<uint32_t*>(scratch(backs->n_words * 4 + 4, kSlotRvBackWords));
+      upload_async(d_recs, backs->recs, backs->n * 12);
+      upload_async(d_words, backs->words, backs->n_words * 4);
+      recs = d_recs, words = d_words;
+    } else {
+      check_injector(inj_index, inj_rows, inj_offsets, inj_values, data_cols * n, n);
+      const size_t n_inj = inj_index[inj_rows];
+      auto* d_idx = static_cast<uint32_t*>(scratch((inj_rows + 1) * 4, kSlotRvInjIndex));
+      auto* d_off = static_cast<uint32_t*>(scratch(n_inj * 4 + 4, kSlotRvInjOffsets));
+      auto* d_val = static_cast<uint32_t*>(scratch(n_inj * 4 + 4, kSlotRvInjValues));
+      upload_async(d_idx, inj_index, (inj_rows + 1) * 4);
+      upload_async(d_off, inj_offsets, n_inj * 4);
+      upload_async(d_val, inj_values, n_inj * 4);
+      idx = d_idx, off = d_off, val = d_val;
+    }
     cyc = rv32im_upload_cycles(cyc, n);
     auto* d_txn = static_cast<rvwg::MemoryTxn*>(scratch(size_t(pf->txns_len) * sizeof(rvwg::MemoryTxn) + 16, kSlotRvwgTxns));
     auto* d_big = static_cast<uint8_t*>(scratch(size_t(pf->bigint_bytes_len) + 16, kSlotRvwgBigint));
@@ -514,14 +572,23 @@ std::vector<uint32_t> prove_trace(int suite, uint32_t po2, uint32_t mode, const 
   }
   auto* ierr = static_cast<uint32_t*>(scratch(16, kSlotRvInitErr));
   HIP_OK(hipMemsetD32Async(ierr, 0u, 4, s));
-  rv32im_prover_inject(s, data.p, n, idx, off, val, inj_rows, data.words, cyc, ierr);
+  // the injector: the CSR list scattered, or the Back records expanded (the same words)
+  auto inject = [&](uint32_t* err) {
+    if (backs)
+      rv32im_inject_backs(s, data.p, n, cyc, inj_rows, recs, backs->n, words, backs->n_words, backs->entries, err);
+    else if (err)
+      rv32im_prover_inject(s, data.p, n, idx, off, val, inj_rows, data.words, cyc, err);
+    else
+      scatter(s, data.p, idx, off, val, inj_rows, data.words);
+  };
+  inject(ierr);
   {
     Span w("witgen");
     // an injector entry outside its row's injected columns: the group as the reference prepares
     // it (hal_generate_witness, witgen/mod.rs:146-162), every word INVALID and the injector scattered
     auto reinit = [&] {
       HIP_OK(hipMemsetD32Async(data.p, 0xFFFFFFFFu, data.words, s));
-      scatter(s, data.p, idx, off, val, inj_rows, data.words);
+      inject(nullptr);
     };
     rv32im_witgen_dev(s, mode, data.p, global.p, n, cyc, txn, pf->txns_len, big, pf->bigint_bytes_len,
                       pf->table_split_cycle, uint32_t(n), true, ierr, reinit);
@@ -646,8 +713,43 @@ const char* r0hip_prove_segment_trace(int suite, uint32_t po2, uint32_t mode, co
   return wrap([&] {
     std::vector<uint32_t> mix;
     auto seal = prove_trace(suite, po2, mode, h_global, h_inj_index, inj_rows, h_inj_offsets, h_inj_values, preflight,
-                            h_bigint, n_bigint, false, &mix, {});
+                            h_bigint, n_bigint, false, &mix, {}, nullptr);
     seal_out(seal, mix, h_seal, seal_cap, seal_len, h_mix_out);
+  });
+}
+
+const char* r0hip_prove_segment_trace_backs(int suite, uint32_t po2, uint32_t mode, const uint32_t* h_global,
+                                            const r0hip_raw_preflight_trace* preflight, const r0hip_backs* backs,
+                                            uint32_t* h_seal, size_t seal_cap, size_t* seal_len, uint32_t* h_mix_out) {
+  return wrap([&] {
+    R0_REQUIRE(po2 >= 2 && po2 <= 24, "r0hip_prove_segment_trace_backs: po2 out of range");
+    const BacksInfo info = check_backs(backs, size_t(1) << po2, "r0hip_prove_segment_trace_backs");
+    const std::vector<r0hip_bigint_back> bigint = backs_bigint_records(*backs, info.n_bigint);
+    const TraceBacks tb{reinterpret_cast<const uint32_t*>(backs->recs), backs->n, backs->words, backs->n_words,
+                        backs->inj_rows, info.entries};
+    std::vector<uint32_t> mix;
+    auto seal = prove_trace(suite, po2, mode, h_global, nullptr, 0, nullptr, nullptr, preflight,
+                            bigint.empty() ? nullptr : bigint.data(), bigint.size(), false, &mix, {}, &tb);
+    seal_out(seal, mix, h_seal, seal_cap, seal_len, h_mix_out);
+  });
+}
+
+const char* r0hip_rv32im_inject_backs(uint32_t* d_data, size_t rows, const void* h_cycles, const r0hip_backs* backs) {
+  return wrap_dev([&] {
+    R0_REQUIRE(d_data, "r0hip_rv32im_inject_backs: d_data is NULL");
+    R0_REQUIRE(rows >= 4 && rows <= (size_t(1) << 24) && (rows & (rows - 1)) == 0,
+               "r0hip_rv32im_inject_backs: rows must be a power of two in [4, 2^24]");
+    const BacksInfo info = check_backs(backs, rows, "r0hip_rv32im_inject_backs");
+    R0_REQUIRE(backs->inj_rows == 0 || h_cycles, "r0hip_rv32im_inject_backs: h_cycles is NULL");
+    if (!deferred_mode()) stage_reset();  // it drains; the deferred arena recycles itself
+    const rvwg::PreflightCycle* d_cycles =
+        rv32im_upload_cycles(static_cast<const rvwg::PreflightCycle*>(h_cycles), backs->inj_rows);
+    auto* d_recs = static_cast<uint32_t*>(scratch(backs->n * 12 + 4, kSlotRvBackRecs));
+    auto* d_words = static_cast<uint32_t*>(scratch(backs->n_words * 4 + 4, kSlotRvBackWords));
+    upload_async(d_recs, backs->recs, backs->n * 12);
+    upload_async(d_words, backs->words, backs->n_words * 4);
+    rv32im_inject_backs(stream(), d_data, rows, d_cycles, backs->inj_rows, d_recs, backs->n, d_words, backs->n_words,
+                        info.entries, nullptr);
   });
 }
 
@@ -660,7 +762,7 @@ const char* r0hip_prove_segment_trace_resident(int suite, uint32_t po2, uint32_t
   return wrap([&] {
     std::vector<uint32_t> mix;
     auto seal = prove_trace(suite, po2, mode, d_global, d_inj_index, inj_rows, d_inj_offsets, d_inj_values,
-                            d_preflight, h_bigint, n_bigint, true, &mix, {});
+                            d_preflight, h_bigint, n_bigint, true, &mix, {}, nullptr);
     seal_out(seal, mix, h_seal, seal_cap, seal_len, h_mix_out);
   });
 }

@@ -29,6 +29,7 @@
 #include <vector>
 
 #include "../../include/r0hip.h"
+#include "backs.h"
 #include "circuit.h"
 #include "devmem.h"
 #include "runtime.h"
@@ -44,7 +45,8 @@ std::vector<uint32_t> prove_trace(int suite, uint32_t po2, uint32_t mode, const 
                                   const uint32_t* inj_index, size_t inj_rows, const uint32_t* inj_offsets,
                                   const uint32_t* inj_values, const r0hip_raw_preflight_trace* pf,
                                   const r0hip_bigint_back* h_bigint, size_t n_bigint, bool resident,
-                                  std::vector<uint32_t>* mix, const std::function<void(hipStream_t)>& inputs_ready);
+                                  std::vector<uint32_t>* mix, const std::function<void(hipStream_t)>& inputs_ready,
+                                  const TraceBacks* backs);
 void check_injector(const uint32_t* index, size_t rows, const uint32_t* offsets, const uint32_t* values,
                     size_t limit, size_t seg_rows);
 
@@ -202,9 +204,11 @@ void upload_trace(TraceSet& b, const r0hip_trace_input& t, size_t n) {
 // The prover's part: prove_trace from the set's device copies. Its stream waits for the set's
 // upload just before the first read of an input; *error (written by the uploader under b.mu)
 // is the job's staging error, rethrown here.
+// backs: the set holds the injector as Back records (a worker's kind-2 job) and not the CSR arrays
 std::vector<uint32_t> prove_staged_trace(TraceSet& b, int suite, uint32_t po2, const r0hip_trace_input& tr,
                                          const r0hip_bigint_back* h_bigint, size_t n_bigint,
-                                         const char* const* error, std::vector<uint32_t>* mix) {
+                                         const char* const* error, std::vector<uint32_t>* mix,
+                                         const TraceBacks* backs = nullptr) {
   r0hip_raw_preflight_trace pf = tr.preflight;  // the set's device copies
   pf.cycles = b.cycles.p;
   pf.txns = pf.txns_len ? b.txns.p : nullptr;
@@ -217,7 +221,15 @@ std::vector<uint32_t> prove_staged_trace(TraceSet& b, int suite, uint32_t po2, c
                          if (*error) throw std::runtime_error(*error);
                        }
                        HIP_OK(hipStreamWaitEvent(st, b.ev, 0));
-                     });
+                     }, backs);
+}
+
+// The null checks of a kind-2 worker job's trace (n = 2^po2); its records are check_backs's.
+void check_backs_trace(const r0hip_trace_input& t, const std::string& who) {
+  const r0hip_raw_preflight_trace& pf = t.preflight;
+  R0_REQUIRE(t.h_global && pf.cycles, who + ": trace job: null argument");
+  R0_REQUIRE((pf.txns_len == 0 || pf.txns) && (pf.bigint_bytes_len == 0 || pf.bigint_bytes),
+             who + ": trace job: null trace array with a nonzero count");
 }
 
 // Trace jobs: the uploader copies job i's trace into a free trace set and hands the set to a
@@ -391,6 +403,12 @@ struct WorkerSet : TraceSet {
   DevBuf ctrl;  // recursion jobs: the control group (allocated at the set's first one)
   r0hip_worker_job* wjob = nullptr;
   size_t cap_inj = 0, cap_txn = 0, cap_big = 0;  // entries, records, bytes
+  // kind-2 jobs: the Back records and their payload words (allocated at the set's first one),
+  // the counts of the uploader's check and the BigInt records it derived for the accumulation
+  DevBuf recs, words;
+  size_t cap_recs = 0, cap_words = 0;
+  BacksInfo backs_info;
+  std::vector<r0hip_bigint_back> backs_bigint;
 };
 
 struct WorkerImpl {
@@ -402,7 +420,8 @@ struct WorkerImpl {
   Queue free_q, ready_q;
   std::mutex mu;  // fifo, finished, next_ticket, outstanding, stopping
   std::condition_variable cv_in, cv_done;
-  std::deque<r0hip_worker_job*> fifo, finished;
+  std::deque<r0hip_worker_job*> finished;
+  std::deque<std::pair<r0hip_worker_job*, BacksInfo>> fifo;  // with the submit check's counts (kind 2)
   uint64_t next_ticket = 0;
   size_t outstanding = 0;
   bool stopping = false;
@@ -428,19 +447,34 @@ struct WorkerImpl {
   }
 
   // the set is free (its last prover drained its stream): make its buffers hold job j
-  void grow(WorkerSet& b, const r0hip_worker_job& j) {
+  void grow(WorkerSet& b, const r0hip_worker_job& j, const BacksInfo& info) {
     const size_t n = size_t(1) << j.po2;
     if (j.kind == R0HIP_JOB_RECURSION) {
       if (b.ctrl.words < 23 * n) b.ctrl = DevBuf(23 * n);
       return;
     }
     const r0hip_trace_input& t = j.trace;
-    // an index that names more entries than the data group has words is refused by run_uploader
-    const size_t n_inj = t.inj_rows <= n ? t.h_inj_index[t.inj_rows] : 0;
-    if (n_inj > b.cap_inj && n_inj <= 211 * n) {
-      b.offsets = DevBuf(n_inj);
-      b.values = DevBuf(n_inj);
-      b.cap_inj = n_inj;
+    if (j.kind == R0HIP_JOB_RV32IM_BACKS) {  // checked at submit: at most n records, n_words below 2^32
+      if (j.backs->n > b.cap_recs) {
+        b.recs = DevBuf(j.backs->n * 3);
+        b.cap_recs = j.backs->n;
+      }
+      if (j.backs->n_words > b.cap_words) {
+        b.words = DevBuf(j.backs->n_words);
+        b.cap_words = j.backs->n_words;
+      }
+      // what the prover reads on the host: the check's counts and the accumulation's BigInt
+      // records, derived from the payloads in one pass
+      b.backs_info = info;
+      b.backs_bigint = backs_bigint_records(*j.backs, info.n_bigint);
+    } else {
+      // an index that names more entries than the data group has words is refused by run_uploader
+      const size_t n_inj = t.inj_rows <= n ? t.h_inj_index[t.inj_rows] : 0;
+      if (n_inj > b.cap_inj && n_inj <= 211 * n) {
+        b.offsets = DevBuf(n_inj);
+        b.values = DevBuf(n_inj);
+        b.cap_inj = n_inj;
+      }
     }
     if (t.preflight.txns_len > b.cap_txn) {
       b.txns = DevBuf(size_t(t.preflight.txns_len) * kTxnWords);
@@ -455,11 +489,13 @@ struct WorkerImpl {
   void run_uploader() {
     for (;;) {
       r0hip_worker_job* j;
+      BacksInfo info;
       {
         std::unique_lock<std::mutex> lk(mu);
         cv_in.wait(lk, [&] { return !fifo.empty() || stopping; });
         if (fifo.empty()) break;
-        j = fifo.front();
+        j = fifo.front().first;
+        info = fifo.front().second;
         fifo.pop_front();
       }
       const long s = free_q.get();
@@ -479,7 +515,7 @@ struct WorkerImpl {
       }
       try {
         ensure_init();
-        grow(b, *j);
+        grow(b, *j, info);
       } catch (const std::exception& e) {
         fail(e.what());
         ok = false;
@@ -490,6 +526,17 @@ struct WorkerImpl {
           if (j->kind == R0HIP_JOB_RECURSION) {
             stage_reset();
             upload_async(b.ctrl.p, j->recursion.h_ctrl, 23 * n * 4);
+            HIP_OK(hipEventRecord(b.ev, stream()));
+          } else if (j->kind == R0HIP_JOB_RV32IM_BACKS) {
+            // the records were checked at submit; no index, offsets or values are staged
+            const r0hip_raw_preflight_trace& pf = j->trace.preflight;
+            stage_reset();  // the previous job's staged copies have landed: the arena is free
+            upload_async(b.glob.p, j->trace.h_global, kGlobalWords * 4);
+            upload_async(b.recs.p, j->backs->recs, j->backs->n * sizeof(r0hip_back));
+            upload_async(b.words.p, j->backs->words, j->backs->n_words * 4);
+            upload_async(b.cycles.p, pf.cycles, n * kCycleWords * 4);
+            upload_async(b.txns.p, pf.txns, size_t(pf.txns_len) * kTxnWords * 4);
+            upload_async(b.bigint.p, pf.bigint_bytes, pf.bigint_bytes_len);
             HIP_OK(hipEventRecord(b.ev, stream()));
           } else {
             check_trace_input(j->trace, j->h_bigint, j->n_bigint, n);
@@ -533,6 +580,14 @@ struct WorkerImpl {
           const r0hip_recursion_input& in = j->recursion;
           seal = prove_recursion(j->suite, j->po2, b.ctrl.p, in.h_wom, in.n_wom, in.h_cycles, in.n_cycles, in.h_iops,
                                  in.n_iops, keyed_noise(key, j->ticket), &mix);
+        } else if (j->kind == R0HIP_JOB_RV32IM_BACKS) {
+          // the set's counts and BigInt records were written by the uploader before the hand-over
+          // (grow); the record and word counts are the caller's, checked at submit
+          const TraceBacks tb{b.recs.p, j->backs->n, b.words.p, j->backs->n_words, j->backs->inj_rows,
+                              b.backs_info.entries};
+          seal = prove_staged_trace(b, j->suite, j->po2, j->trace,
+                                    b.backs_bigint.empty() ? nullptr : b.backs_bigint.data(), b.backs_bigint.size(),
+                                    &j->error, &mix, &tb);
         } else {
           seal = prove_staged_trace(b, j->suite, j->po2, j->trace, j->h_bigint, j->n_bigint, &j->error, &mix);
         }
@@ -883,8 +938,10 @@ extern "C" const char* r0hip_worker_submit(r0hip_worker* w, r0hip_worker_job* jo
   return guarded([&] {
     R0_REQUIRE(w && job, "r0hip_worker_submit: null argument");
     WorkerImpl& m = w->impl;
-    R0_REQUIRE(job->kind == R0HIP_JOB_RV32IM_TRACE || job->kind == R0HIP_JOB_RECURSION,
+    R0_REQUIRE(job->kind == R0HIP_JOB_RV32IM_TRACE || job->kind == R0HIP_JOB_RECURSION ||
+                   job->kind == R0HIP_JOB_RV32IM_BACKS,
                "r0hip_worker_submit: unknown job kind");
+    BacksInfo info;
     R0_REQUIRE(job->suite >= 0 && job->suite <= 2, "r0hip_worker_submit: unknown hash suite");
     R0_REQUIRE(job->po2 <= m.max_po2, "r0hip_worker_submit: po2 " + std::to_string(job->po2) +
                                           " above the worker's max_po2 " + std::to_string(m.max_po2));
@@ -897,6 +954,10 @@ extern "C" const char* r0hip_worker_submit(r0hip_worker* w, r0hip_worker_job* jo
       R0_REQUIRE(in.h_ctrl && (in.h_wom || !in.n_wom) && (in.h_cycles || !in.n_cycles) && (in.h_iops || !in.n_iops) &&
                      (in.h_code_roots || !in.n_code_roots),
                  "r0hip_worker_submit: recursion job: null argument");
+    } else if (job->kind == R0HIP_JOB_RV32IM_BACKS) {
+      R0_REQUIRE(job->po2 >= 2, "r0hip_worker_submit: po2 out of range");
+      check_backs_trace(job->trace, "r0hip_worker_submit");
+      info = check_backs(job->backs, size_t(1) << job->po2, "r0hip_worker_submit");
     } else {
       const r0hip_trace_input& t = job->trace;
       R0_REQUIRE(job->po2 >= 2, "r0hip_worker_submit: po2 out of range");
@@ -916,7 +977,7 @@ extern "C" const char* r0hip_worker_submit(r0hip_worker* w, r0hip_worker_job* jo
       R0_REQUIRE(!m.stopping, "r0hip_worker_submit: the worker is shutting down");
       job->ticket = m.next_ticket++;
       m.outstanding++;
-      m.fifo.push_back(job);
+      m.fifo.emplace_back(job, info);
     }
     m.cv_in.notify_one();
   });

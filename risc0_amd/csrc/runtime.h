@@ -130,6 +130,9 @@ enum ScratchSlot : int {
   kSlotRvInjOffsets = 81,
   kSlotRvInjValues = 82,
   kSlotRvInitErr = 87,
+  // the injector as Back records (api.cpp): the records and their payload words
+  kSlotRvBackRecs = 93,
+  kSlotRvBackWords = 94,
 };
 
 // Scratch buffer reused across calls (grown on demand; stream-ordered use only).

@@ -57,6 +57,20 @@ constexpr uint32_t kErrMajor = 0x2000Bu;         // a cycle's major outside the 
 // writes only its own row, witgen/mod.rs:352-377; the init pass writes a row per lane)
 constexpr uint32_t kErrInjectorRow = 0x2000Cu;
 
+// The injector's columns by source (build_injector, witgen/mod.rs:226-270), emitted by
+// tools/gen_rv32im_witgen.py from circuits/rv32im.witgen.json. A Back record's kind k (include/
+// r0hip.h R0HIP_BACK_*; 0 is no kind) has plain[k] payload words that go to one column each,
+// cols[first[k] ..], then bits[k] words that go out bit by bit from the columns that follow
+// (Injector::set_u32_bits). wrong_arms[k]: bit a set when a record of kind k on a row of
+// instruction arm a sets a column that arm does not take from the injector.
+constexpr uint32_t kBackKinds = 5;
+struct BackTables {
+  uint8_t cycle_cols[5];  // cycle, next_pc_low, next_pc_high, next_state_0, next_machine_mode
+  uint8_t plain[kBackKinds], bits[kBackKinds], first[kBackKinds];
+  uint16_t wrong_arms[kBackKinds];
+  uint8_t cols[74];
+};
+
 struct Args {
   uint32_t* data;    // DATA x rows, column-major (MutableBufObj over Buffer<checked>)
   uint32_t* global;  // the global vector (GlobalBufObj over Buffer<checked>)
@@ -361,6 +375,18 @@ void rv32im_prover_groups_fill(hipStream_t s, uint32_t* data, uint32_t* code, ui
 void rv32im_prover_inject(hipStream_t s, uint32_t* data, size_t rows, const uint32_t* index, const uint32_t* offsets,
                           const uint32_t* values, size_t inj_rows, uint64_t limit, const rvwg::PreflightCycle* d_cycles,
                           uint32_t* err);
+// The same injection from the preflight's Back records (include/r0hip.h, r0hip_backs), every
+// array in device memory: a cycle pass (one lane per row r < inj_rows: the five set_cycle columns
+// from r and d_cycles[r]) and a back pass (one lane per record: its payload words, plain u32,
+// encoded and stored in its kind's columns). d_recs: n_recs records of three words (row, kind,
+// word). A record whose kind, row or payload range is out of bounds writes nothing (the host has
+// refused it, rv32im_check_backs). err (4 words, may be null): word 3 is set by a record on a row
+// whose arm does not take the kind's columns from the injector, as rv32im_prover_inject sets it.
+// entries: the (offset, value) pairs the records expand to, for the timing's byte count.
+void rv32im_inject_backs(hipStream_t s, uint32_t* data, size_t rows, const rvwg::PreflightCycle* d_cycles,
+                         size_t inj_rows, const uint32_t* d_recs, size_t n_recs, const uint32_t* d_words,
+                         size_t n_words, size_t entries, uint32_t* err);
+const rvwg::BackTables& rv32im_witgen_back_tables();  // generated
 // the same from host preflight arrays (uploaded first), as RawPreflightTrace hands them over
 void rv32im_witgen(hipStream_t s, uint32_t mode, uint32_t* data, uint32_t* global, size_t rows,
                    const rvwg::PreflightCycle* h_cycles, const rvwg::MemoryTxn* h_txns, size_t n_txns,

@@ -226,6 +226,66 @@ __global__ __launch_bounds__(kMergeThreads) void prover_inject_kernel(uint32_t* 
   }
 }
 
+// The injector from the preflight's Back records (rv32im_witgen.h, rv32im_inject_backs): what
+// build_injector computes row by row on the host (witgen/mod.rs:226-270) and hal.scatter writes.
+// Both passes store column-major with consecutive rows on consecutive lanes: the cycle pass has a
+// lane per row; the back pass a lane per record, and records are in row order, so a run of SHA-2
+// or Poseidon2 cycles is a run of lanes whose stores to one column fill whole lines.
+
+// Injector::set_cycle (mod.rs:353-365): one lane per row r < inj_rows
+__global__ __launch_bounds__(kMergeThreads) void backs_cycle_kernel(uint32_t* data, uint32_t rows,
+                                                                   const rvwg::PreflightCycle* cycles,
+                                                                   uint32_t inj_rows, rvwg::BackTables T) {
+  const uint32_t r = blockIdx.x * kMergeThreads + threadIdx.x;
+  if (r >= inj_rows) return;
+  const uint32_t pc = cycles[r].pc, state = cycles[r].state, mm = cycles[r].machine_mode;
+  const uint32_t v[5] = {r, pc & 0xFFFFu, pc >> 16, state, mm};
+#pragma unroll
+  for (uint32_t k = 0; k < 5; k++) data[uint64_t(T.cycle_cols[k]) * rows + r] = rvwg::from_u32(v[k]);
+}
+
+// one record's payload into the columns of its kind (a compile-time constant at each call, so the
+// table reads are uniform): Injector::set per plain word, Injector::set_u32_bits per bit word
+__device__ __forceinline__ void back_expand(uint32_t* data, uint32_t rows, uint32_t row, const uint32_t* words,
+                                            uint64_t n_words, uint32_t at, uint32_t arm, uint32_t* err,
+                                            const rvwg::BackTables& T, const uint32_t kind) {
+  const uint8_t* col = T.cols + T.first[kind];
+  const uint32_t np = T.plain[kind], nb = T.bits[kind];
+  if (uint64_t(at) + np + nb > n_words) return;
+  if (err && arm < rvwg::kMajors && ((T.wrong_arms[kind] >> arm) & 1u)) atomicOr(err + 3, 1u);
+  const uint32_t* w = words + at;
+  for (uint32_t k = 0; k < np; k++) data[uint64_t(col[k]) * rows + row] = rvwg::from_u32(w[k]);
+  for (uint32_t k = 0; k < nb; k++) {
+    const uint32_t v = w[np + k], base = col[np + k];
+#pragma unroll 8
+    for (uint32_t b = 0; b < 32; b++) data[uint64_t(base + b) * rows + row] = (v >> b) & 1u ? kOne : 0u;
+  }
+}
+
+// one lane per record (row, kind, word). The host has checked every record; a lane still writes
+// nothing for a kind outside 1..4, a row at or past inj_rows (<= rows) or a payload that ends past
+// n_words, so no read or store leaves the arrays. err[3]: as prover_inject_kernel sets it.
+__global__ __launch_bounds__(kMergeThreads) void backs_expand_kernel(uint32_t* data, uint32_t rows,
+                                                                    const uint32_t* recs, uint32_t n_recs,
+                                                                    const uint32_t* words, uint64_t n_words,
+                                                                    uint32_t inj_rows,
+                                                                    const rvwg::PreflightCycle* cycles,
+                                                                    rvwg::BackTables T, uint32_t* err) {
+  const uint32_t i = blockIdx.x * kMergeThreads + threadIdx.x;
+  if (i >= n_recs) return;
+  const uint32_t row = recs[3 * size_t(i)], kind = recs[3 * size_t(i) + 1], at = recs[3 * size_t(i) + 2];
+  if (row >= inj_rows) return;
+  // a major past the arms fails in the bucket kernel
+  const uint32_t arm = err ? uint32_t(cycles[row].major) : rvwg::kMajors;
+  switch (kind) {
+    case 1: back_expand(data, rows, row, words, n_words, at, arm, err, T, 1); break;
+    case 2: back_expand(data, rows, row, words, n_words, at, arm, err, T, 2); break;
+    case 3: back_expand(data, rows, row, words, n_words, at, arm, err, T, 3); break;
+    case 4: back_expand(data, rows, row, words, n_words, at, arm, err, T, 4); break;
+    default: break;
+  }
+}
+
 }  // namespace
 
 namespace {
@@ -279,6 +339,29 @@ void rv32im_prover_inject(hipStream_t s, uint32_t* data, size_t rows, const uint
   hipLaunchKernelGGL(prover_inject_kernel, dim3(uint32_t((inj_rows + kMergeThreads - 1) / kMergeThreads)),
                      dim3(kMergeThreads), 0, s, data, uint32_t(rows), injected_cols(), index, offsets, values,
                      uint32_t(inj_rows), limit, d_cycles, uint32_t(__builtin_ctzll(rows)), err);
+  HIP_OK(hipGetLastError());
+}
+
+void rv32im_inject_backs(hipStream_t s, uint32_t* data, size_t rows, const rvwg::PreflightCycle* d_cycles,
+                         size_t inj_rows, const uint32_t* d_recs, size_t n_recs, const uint32_t* d_words,
+                         size_t n_words, size_t entries, uint32_t* err) {
+  R0_REQUIRE(rows >= 4 && rows <= (size_t(1) << 24) && (rows & (rows - 1)) == 0 && inj_rows <= rows,
+             "rv32im_inject_backs: bad shape");
+  R0_REQUIRE(n_recs <= inj_rows && (inj_rows == 0 || d_cycles) && (n_recs == 0 || (d_recs && d_words)),
+             "rv32im_inject_backs: bad arguments");
+  if (inj_rows == 0) return;
+  const rvwg::BackTables& T = rv32im_witgen_back_tables();
+  // read: pc, state and machine mode per row, the records and each payload word once;
+  // written: five words per row and one per expanded entry
+  KScope ks("rv32im_backs_inject",
+            double(inj_rows) * (12.0 + 5 * 4.0) + double(n_recs) * 12.0 + double(n_words) * 4.0 + double(entries) * 4.0);
+  hipLaunchKernelGGL(backs_cycle_kernel, dim3(uint32_t((inj_rows + kMergeThreads - 1) / kMergeThreads)),
+                     dim3(kMergeThreads), 0, s, data, uint32_t(rows), d_cycles, uint32_t(inj_rows), T);
+  HIP_OK(hipGetLastError());
+  if (n_recs == 0) return;
+  hipLaunchKernelGGL(backs_expand_kernel, dim3(uint32_t((n_recs + kMergeThreads - 1) / kMergeThreads)),
+                     dim3(kMergeThreads), 0, s, data, uint32_t(rows), d_recs, uint32_t(n_recs), d_words,
+                     uint64_t(n_words), uint32_t(inj_rows), d_cycles, T, err);
   HIP_OK(hipGetLastError());
 }
 

@@ -106,6 +106,9 @@ def _declare(L):
                                                u32p, sz, C.POINTER(sz), u32p],
         "r0hip_prove_segment_trace": [C.c_int, C.c_uint32, C.c_uint32, u32p, u32p, sz, u32p, u32p, vp, vp, sz, u32p,
                                       sz, C.POINTER(sz), u32p],
+        "r0hip_rv32im_inject_backs": [vp, sz, vp, vp],
+        "r0hip_prove_segment_trace_backs": [C.c_int, C.c_uint32, C.c_uint32, u32p, vp, vp, u32p, sz, C.POINTER(sz),
+                                            u32p],
         "r0hip_prove_recursion": [C.c_int, C.c_uint32, vp, u32p, sz, u32p, sz, u32p, sz, C.c_uint64, u32p, sz,
                                   C.POINTER(sz), u32p],
         "r0hip_prove_recursion_keyed": [C.c_int, C.c_uint32, vp, u32p, sz, u32p, sz, u32p, sz, u32p, C.c_uint64, u32p,
@@ -651,6 +654,72 @@ def prove_segment_trace(hal, po2, glob, inj_index, inj_offsets, inj_values, cycl
     return seal[: n.value].copy(), mix
 
 
+class Back(C.Structure):
+    """struct r0hip_back (include/r0hip.h): one row's Back record (witgen/preflight.rs:47-57);
+    `word` is the index of its payload's first word"""
+    _fields_ = [("row", C.c_uint32), ("kind", C.c_uint32), ("word", C.c_uint32)]
+
+
+class BacksStruct(C.Structure):
+    """struct r0hip_backs (include/r0hip.h): the injector as the preflight's Back records"""
+    _fields_ = [("recs", C.c_void_p), ("n", C.c_size_t), ("words", C.c_void_p), ("n_words", C.c_size_t),
+                ("inj_rows", C.c_size_t)]
+
+
+BACK_ECALL, BACK_POSEIDON2, BACK_SHA2, BACK_BIGINT = 1, 2, 3, 4
+#: payload words of each record kind (R0HIP_BACK_*)
+BACK_WORDS = {BACK_ECALL: 3, BACK_POSEIDON2: 39, BACK_SHA2: 10, BACK_BIGINT: 22}
+
+
+class Backs:
+    """r0hip_backs over numpy arrays, kept alive with it: recs is (n, 3) uint32 rows of (row, kind,
+    word), words the payloads as plain u32, inj_rows the rows that get the set_cycle columns. The
+    arrays are kept as given when they are contiguous uint32 (page-locked views copy at full
+    rate); n / n_words default to the arrays' sizes."""
+
+    def __init__(self, recs, words, inj_rows, n=None, n_words=None):
+        u = lambda a: a if isinstance(a, np.ndarray) and a.dtype == np.uint32 and a.flags.c_contiguous \
+            else np.ascontiguousarray(a, dtype=np.uint32)
+        self.recs, self.words, self.inj_rows = u(recs).reshape(-1, 3), u(words).reshape(-1), int(inj_rows)
+        self.struct = BacksStruct(self.recs.ctypes.data if self.recs.size else None,
+                                  self.recs.shape[0] if n is None else n,
+                                  self.words.ctypes.data if self.words.size else None,
+                                  self.words.size if n_words is None else n_words, self.inj_rows)
+
+    def nbytes(self):
+        return self.recs.nbytes + self.words.nbytes
+
+
+def rv32im_inject_backs(data, rows, cycles, backs):
+    """r0hip_rv32im_inject_backs: build_injector plus hal.scatter from the Back records. data is
+    the data group (211 x rows) on the device, cycles the preflight's RawPreflightCycle array
+    (at least backs.inj_rows records), backs a Backs."""
+    cyc = np.ascontiguousarray(cycles)
+    assert backs.inj_rows > rows or cyc.nbytes >= 36 * backs.inj_rows  # inj_rows > rows is refused unread
+    check(lib().r0hip_rv32im_inject_backs(data.ptr, rows, cyc.ctypes.data if cyc.nbytes else None,
+                                          C.byref(backs.struct)))
+
+
+def prove_segment_trace_backs(hal, po2, glob, backs, cycles, txns, table_split, bigint=None, mode=0,
+                              seal_cap=1 << 24):
+    """r0hip_prove_segment_trace_backs: prove_segment_trace with the injector as a Backs (the
+    expansion runs on the device, and the accumulation's BigInt records come from the payloads).
+    Returns (seal, mix)."""
+    g = np.ascontiguousarray(glob, dtype=np.uint32)
+    cyc, tx = np.ascontiguousarray(cycles), np.ascontiguousarray(txns)
+    bi = np.ascontiguousarray(bigint if bigint is not None else np.zeros(0, np.uint8), dtype=np.uint8)
+    pf = RawPreflightTrace(cyc.ctypes.data, tx.ctypes.data if tx.nbytes else None, bi.ctypes.data if bi.size else None,
+                           tx.nbytes // 20, bi.size, table_split)
+    seal = np.zeros(seal_cap, dtype=np.uint32)
+    n = C.c_size_t(0)
+    mix = np.zeros(36, dtype=np.uint32)
+    check(lib().r0hip_prove_segment_trace_backs(hal.suite, po2, mode, g.ctypes.data_as(u32p), C.byref(pf),
+                                                None if backs is None else C.byref(backs.struct),
+                                                seal.ctypes.data_as(u32p), seal_cap, C.byref(n),
+                                                mix.ctypes.data_as(u32p)))
+    return seal[: n.value].copy(), mix
+
+
 class ResidentTrace:
     """a preflight trace, its injector and global vector uploaded once to device memory, for
     r0hip_prove_segment_trace_resident (the benchmark's inputs-in-HBM form of
@@ -821,10 +890,31 @@ class WorkerJobStruct(C.Structure):
                 ("h_bigint", C.c_void_p), ("n_bigint", C.c_size_t), ("recursion", RecursionInput),
                 ("user", C.c_void_p), ("h_seal", C.c_void_p), ("seal_cap", C.c_size_t), ("seal_len", C.c_size_t),
                 ("h_mix_out", C.c_void_p), ("error", C.c_void_p), ("verified", C.c_int), ("verify_ms", C.c_double),
-                ("prove_ms", C.c_double), ("ticket", C.c_uint64)]
+                ("prove_ms", C.c_double), ("ticket", C.c_uint64), ("backs", C.c_void_p)]
 
 
-JOB_RV32IM_TRACE, JOB_RECURSION = 0, 1
+JOB_RV32IM_TRACE, JOB_RECURSION, JOB_RV32IM_BACKS = 0, 1, 2
+
+
+class BacksJob:
+    """one rv32im segment as the worker's kind-2 job takes it: the global vector, the injector
+    as a Backs, the cycle and transaction records and the BigInt bytes. No injector arrays and
+    no BigInt records: both come from the Back records. Arrays are kept as given."""
+
+    def __init__(self, glob, backs, cycles, txns, table_split, bigint=None, mode=0):
+        self.glob = glob if isinstance(glob, np.ndarray) and glob.dtype == np.uint32 and glob.flags.c_contiguous \
+            else np.ascontiguousarray(glob, dtype=np.uint32)
+        self.backs = backs
+        self.cycles, self.txns = np.ascontiguousarray(cycles), np.ascontiguousarray(txns)
+        self.bigint = None if bigint is None or not len(bigint) else np.ascontiguousarray(bigint, dtype=np.uint8)
+        pf = RawPreflightTrace(self.cycles.ctypes.data, self.txns.ctypes.data if self.txns.nbytes else None,
+                               None if self.bigint is None else self.bigint.ctypes.data, self.txns.nbytes // 20,
+                               0 if self.bigint is None else self.bigint.size, table_split)
+        self.struct = TraceInput(mode, self.glob.ctypes.data, None, 0, None, None, pf)
+
+    def h2d_bytes(self):
+        return sum(a.nbytes for a in (self.glob, self.cycles, self.txns)) + self.backs.nbytes() + \
+            (0 if self.bigint is None else self.bigint.nbytes)
 
 
 class Worker:
@@ -898,6 +988,16 @@ class Worker:
         if trace.backs is not None:
             job.h_bigint, job.n_bigint = C.cast(trace.backs, C.c_void_p).value, len(trace.backs)
         return self._submit(job, 36, trace)
+
+    def submit_backs(self, job, po2, suite=None):
+        """queue one rv32im prove_core from a BacksJob (kind R0HIP_JOB_RV32IM_BACKS) at segment
+        size 2^po2; returns its ticket. A bad record is refused here (R0HipError)."""
+        wj = WorkerJobStruct()
+        wj.kind, wj.po2 = JOB_RV32IM_BACKS, po2
+        wj.suite = self.hal.suite if suite is None else (SUITES[suite] if isinstance(suite, str) else int(suite))
+        wj.trace = job.struct
+        wj.backs = None if job.backs is None else C.addressof(job.backs.struct)
+        return self._submit(wj, 36, job)
 
     def submit_recursion(self, po2, ctrl, wom, cycles, iops, code_roots=None, suite=None):
         """queue one recursion proof from the program's control group (23 x 2^po2 host words)
