@@ -502,6 +502,64 @@ const char* r0hip_prove_recursion_keyed(int suite, uint32_t po2, const uint32_t*
                                         uint64_t stream_id, uint32_t* h_seal, size_t seal_cap, size_t* seal_len,
                                         uint32_t* h_mix_out);
 
+/* ---- resident recursion programs (circuit/recursion/src/prove/program.rs:33-104; the control
+ * group of WitnessGenerator::new, prove/witgen.rs:57-67; its commitment, zkp/src/prove/prover.rs:
+ * 81-108) ----
+ * r0vm proves a handful of fixed programs (lift, join, resolve, ...) thousands of times, and the
+ * control group and its commitment depend only on (program, po2, suite). A handle makes both
+ * once; every proof from it skips the host transposition, the 23 x 2^po2 word upload and the
+ * control group's NTTs, row hashes and Merkle tree. */
+typedef struct r0hip_recursion_program r0hip_recursion_program;
+#define R0HIP_CODE_ENCODED    0  /* plain u32 words as a .zkr holds them; Elem::from per word (program.rs:50-58) */
+#define R0HIP_CODE_MONTGOMERY 1  /* Program.code as the Rust side holds it: canonical Montgomery words */
+/* Program::from_encoded + WitnessGenerator::new's control group + Program::compute_control_id
+ * (program.rs:46-104, witgen.rs:57-67). h_code: n_words = 23 * code_rows words, row-major, 23
+ * per program row (Program.code and the .zkr stream), in the given form. On the device the rows
+ * become the control group (column-major, 2^po2 rows, rows from code_rows on zero), which is
+ * committed as every proof commits it (interpolate + zk shift, 4x evaluate, row hashes, Merkle
+ * tree). The handle keeps the group, its coefficients, evaluations and node heap in four
+ * dedicated allocations (not pool blocks; counted by r0hip_mem_stats, live and reserved) that
+ * nothing writes after this call, plus a host copy of the root: the control id. Complete on
+ * return: any stream of any thread may read the handle. Refused on the host, before any device
+ * call, with the argument (and for a word its index) in the message: a NULL out or h_code, an
+ * unknown suite or form, po2 outside 11..24, n_words 0 or not a multiple of 23, more than
+ * 2^po2 - 1024 rows (program.rs:56-57), and in the Montgomery form a word >= p. In the encoded
+ * form every u32 is legal (Elem::from reduces it). */
+/* [drains] */
+const char* r0hip_recursion_program_create(r0hip_recursion_program** out, int suite, uint32_t po2,
+                                           const uint32_t* h_code, size_t n_words, int form);
+/* What a handle holds; every out pointer may be NULL. control_id: the control group's Merkle
+ * root (program.rs:74-104), the digest r0hip_verify_seal reports as the code root of a seal
+ * made from this program. device_bytes: the four allocations, 4 * (23 + 23 + 92) * 2^po2 for the
+ * group, coefficients and evaluations plus 64 * 4 * 2^po2 for the node heap. */
+/* [host-only] */
+const char* r0hip_recursion_program_info(const r0hip_recursion_program* program, int* suite, uint32_t* po2,
+                                         size_t* code_rows, uint32_t control_id[8], uint64_t* device_bytes);
+/* The handle's control group on the device (23 columns x 2^po2 words), read-only, valid until
+ * r0hip_recursion_program_destroy: what r0hip_recursion_witgen, r0hip_recursion_accum and
+ * r0hip_prove_recursion_keyed take as d_ctrl. */
+/* [host-only] */
+const char* r0hip_recursion_program_ctrl(const r0hip_recursion_program* program, const uint32_t** d_ctrl);
+/* RecursionProverImpl::prove (circuit/recursion/src/prove/mod.rs:160-230) from a handle:
+ * r0hip_prove_recursion_keyed's sequence (witness generation from the handle's control group,
+ * keyed ChaCha20 noise, zeroize, data commit, mix, accumulation, accum commit, finalize) with
+ * the control group's commitment taken from the handle; its root enters the transcript where
+ * the commit would put it. Seal and mix are word for word those of r0hip_prove_recursion_keyed
+ * on the same control group, key and stream_id. n_cycles must equal the handle's code_rows
+ * (witgen.rs:80). No code commit is left to move to a side stream: with r0hip_set_proof_streams
+ * >= 2 the call runs as at n = 1. Any number of threads may prove from one handle at once; each
+ * proof holds a use count until it returns. */
+/* [drains] */
+const char* r0hip_prove_recursion_program(const r0hip_recursion_program* program, const uint32_t* h_wom, size_t n_wom,
+                                          const uint32_t* h_cycles, size_t n_cycles, const uint32_t* h_iops,
+                                          size_t n_iops, const uint32_t* h_key, uint64_t stream_id, uint32_t* h_seal,
+                                          size_t seal_cap, size_t* seal_len, uint32_t* h_mix_out);
+/* Frees the handle and its device memory (after it and r0hip_trim, r0hip_mem_stats' live bytes
+ * are what they were before create). While a proof runs from the handle or a worker job that
+ * names it has not been handed back, it returns an error and frees nothing. */
+/* [drains] */
+const char* r0hip_recursion_program_destroy(r0hip_recursion_program* program);
+
 /* ---- segment pipeline (r0vm's per-GPU worker queue, r0vm/src/actors/worker.rs:75-76, over the
  * zkvm's per-segment prove loop, zkvm/src/host/server/prove/prover_impl.rs:84-94) ----
  * Proves njobs segments of one (circuit, suite, po2) from HOST witness groups: an uploader thread
@@ -600,8 +658,20 @@ const char* r0hip_prove_trace_segments(int suite, uint32_t po2, r0hip_trace_job*
  * are derived from the payloads), stage only the records and the payload words, and give the
  * seal of r0hip_prove_segment_trace_backs. Their records are checked in r0hip_worker_submit, as
  * r0hip_rv32im_inject_backs checks them; the r0hip_backs struct stays valid like the arrays.
+ * Jobs of kind R0HIP_JOB_RECURSION_PROGRAM are recursion jobs from a resident program
+ * (r0hip_recursion_program_create). Such a job is an r0hip_worker_program_job, the job struct
+ * followed by the handle; r0hip_worker_submit takes the address of its `job` member (the
+ * struct's own address) and r0hip_worker_wait hands that address back. r0hip_worker_job itself
+ * keeps its size and every offset, so callers built against it are untouched. They use recursion.h_wom, h_cycles, h_iops and
+ * the allow-list, ignore recursion.h_ctrl, stage no control group (the set's control buffer is
+ * not grown for them) and give the seal of r0hip_prove_recursion_program with the worker's key
+ * and stream_id = the ticket, which is also the kind-1 seal of the same input and ticket.
+ * r0hip_worker_submit refuses a NULL handle, a handle whose suite or po2 differs from the job's
+ * and n_cycles != the handle's code_rows; an accepted job holds a use count on the handle until
+ * r0hip_worker_wait can hand it back (r0hip_recursion_program_destroy is refused meanwhile).
  * With verify, every seal goes through r0hip_verify_seal (recursion: against the
- * job's h_code_roots allow-list); a failed check sets "receipt verification failed: ..." on
+ * job's h_code_roots allow-list; a kind-3 job with n_code_roots = 0: against the handle's own
+ * control id); a failed check sets "receipt verification failed: ..." on
  * that job alone.
  * r0hip_worker_wait returns the next finished job in completion order, each job exactly once.
  * *done = NULL with no error: the timeout passed (timeout_ms = 0 polls, < 0 waits without
@@ -614,6 +684,7 @@ typedef struct r0hip_worker r0hip_worker;
 #define R0HIP_JOB_RV32IM_TRACE 0
 #define R0HIP_JOB_RECURSION 1
 #define R0HIP_JOB_RV32IM_BACKS 2
+#define R0HIP_JOB_RECURSION_PROGRAM 3
 typedef struct r0hip_recursion_input {
   const uint32_t* h_ctrl;        /* control group, 23 columns x 2^po2, host */
   const uint32_t* h_wom;         /* as r0hip_recursion_witgen takes them */
@@ -632,7 +703,7 @@ typedef struct r0hip_worker_job {
   r0hip_trace_input trace;            /* kind 0; kind 2: mode, h_global and preflight */
   const r0hip_bigint_back* h_bigint;  /* kind 0: the trace's BigInt backs (NULL, 0 if none) */
   size_t n_bigint;
-  r0hip_recursion_input recursion;    /* kind 1 */
+  r0hip_recursion_input recursion;    /* kind 1; kind 3: all but h_ctrl */
   void* user;                         /* untouched */
   uint32_t* h_seal;                   /* out: the seal (seal_cap words), its length in seal_len */
   size_t seal_cap;
@@ -646,6 +717,12 @@ typedef struct r0hip_worker_job {
   uint64_t ticket;                    /* out: submission number, from 0 */
   const r0hip_backs* backs;           /* kind 2: the Back records (read for no other kind) */
 } r0hip_worker_job;
+/* a job of kind R0HIP_JOB_RECURSION_PROGRAM: r0hip_worker_job with the handle appended. Submit
+ * &pj.job; a job of that kind is always read as this struct, a job of any other kind never is. */
+typedef struct r0hip_worker_program_job {
+  r0hip_worker_job job;                   /* kind 3; recursion: all but h_ctrl */
+  const r0hip_recursion_program* program; /* the resident program */
+} r0hip_worker_program_job;
 /* [drains] */
 const char* r0hip_worker_create(r0hip_worker** out, uint32_t max_po2, uint32_t in_flight, int verify,
                                 const uint32_t* h_noise_key);

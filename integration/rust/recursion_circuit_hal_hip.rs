@@ -18,6 +18,31 @@ use crate::{REGISTER_GROUP_ACCUM, REGISTER_GROUP_CTRL, REGISTER_GROUP_DATA, GLOB
 
 pub struct HipRecursionCircuitHal<HS: HipHash> { _hal: Rc<HipHal<HS>> }
 
+// Resident programs (r0hip_recursion_program_*). r0vm proves a handful of fixed programs (lift,
+// join, resolve, identity_p254, ...) thousands of times, and a program's control group and its
+// commitment depend only on (program, po2, suite). A HipHal that proves whole recursion proofs
+// through the fused call keeps one handle per program here, beside the HAL it belongs to:
+//
+//     programs: RefCell<HashMap<(Digest, usize), *mut R0HipRecursionProgram>>,  // (control_id, po2)
+//
+// filled on first use in RecursionProverImpl::prove (prove/mod.rs:160-230), where the reference
+// runs WitnessGenerator::new's host transposition (witgen.rs:57-67) and commits the control group:
+//
+//     let h = *programs.entry((program.control_id, po2)).or_insert_with(|| {
+//         let mut h = std::ptr::null_mut();   // Program.code is Montgomery words, 23 per row
+//         ffi_wrap(|| unsafe { r0hip_recursion_program_create(&mut h, HS::SUITE, po2 as u32,
+//             program.code.as_ptr().cast(), program.code.len(), R0HIP_CODE_MONTGOMERY) }).unwrap();
+//         h
+//     });
+//     r0hip_prove_recursion_program(h, wom, n_wom, cycles, n_cycles, iops, n_iops, null(), task_id, ..)
+//     // on the worker: R0HipWorkerProgramJob { job: R0HipWorkerJob { kind: R0HIP_JOB_RECURSION_PROGRAM,
+//     //                 recursion: {..}, .. }, program: h }, submitted as &mut pj.job
+//
+// r0hip_recursion_program_info's control_id is Program::compute_control_id (program.rs:74-104) for
+// the HAL's suite. The per-op path below keeps taking `ctrl` as a buffer; r0hip_recursion_program_ctrl
+// gives the handle's control group for it. Drop: r0hip_recursion_program_destroy per handle, after
+// the worker that was given it (destroy is refused while a job or a proof still holds the handle).
+
 impl<HS: HipHash> CircuitWitnessGenerator<HipHal<HS>> for HipRecursionCircuitHal<HS> {
     fn generate_witness(&self, _mode: StepMode, total_cycles: u32, preflight: &RawPreflightTrace,
                         ctrl: &BufferImpl<BabyBearElem>, data: &BufferImpl<BabyBearElem>,

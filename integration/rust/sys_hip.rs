@@ -91,6 +91,17 @@ pub struct R0HipWorker {
 pub const R0HIP_JOB_RV32IM_TRACE: u32 = 0;
 pub const R0HIP_JOB_RECURSION: u32 = 1;
 pub const R0HIP_JOB_RV32IM_BACKS: u32 = 2;
+pub const R0HIP_JOB_RECURSION_PROGRAM: u32 = 3;
+
+/// Forms of the code words r0hip_recursion_program_create takes (R0HIP_CODE_*).
+pub const R0HIP_CODE_ENCODED: c_int = 0; // plain u32 words of a .zkr (Elem::from per word)
+pub const R0HIP_CODE_MONTGOMERY: c_int = 1; // Program.code: canonical Montgomery words
+
+/// A recursion program resident on the device (struct r0hip_recursion_program, opaque).
+#[repr(C)]
+pub struct R0HipRecursionProgram {
+    _private: [u8; 0],
+}
 
 /// Record kinds of R0HipBack (R0HIP_BACK_*) and their payload sizes in words.
 pub const R0HIP_BACK_ECALL: u32 = 1; // 3: s0, s1, s2
@@ -157,6 +168,14 @@ pub struct R0HipWorkerJob {
     pub prove_ms: f64,
     pub ticket: u64,
     pub backs: *const R0HipBacks,
+}
+
+/// A job of kind R0HIP_JOB_RECURSION_PROGRAM (struct r0hip_worker_program_job): the job with the
+/// handle appended. Submit `&mut pj.job`; r0hip_worker_wait hands that address back.
+#[repr(C)]
+pub struct R0HipWorkerProgramJob {
+    pub job: R0HipWorkerJob,
+    pub program: *const R0HipRecursionProgram,
 }
 
 #[link(name = "r0hip")]
@@ -487,6 +506,44 @@ unsafe extern "C" {
         seal_len: *mut usize,
         h_mix_out: *mut u32,
     ) -> *const c_char;
+    // ---- resident recursion programs (program.rs:33-104, witgen.rs:57-67) ----
+    /// the control group and its commitment from Program.code, made once (h_code: 23 words per row)
+    pub fn r0hip_recursion_program_create(
+        out: *mut *mut R0HipRecursionProgram,
+        suite: c_int,
+        po2: u32,
+        h_code: *const u32,
+        n_words: usize,
+        form: c_int,
+    ) -> *const c_char;
+    /// every out pointer may be null; control_id is Program::compute_control_id's digest
+    pub fn r0hip_recursion_program_info(
+        program: *const R0HipRecursionProgram,
+        suite: *mut c_int,
+        po2: *mut u32,
+        code_rows: *mut usize,
+        control_id: *mut u32,
+        device_bytes: *mut u64,
+    ) -> *const c_char;
+    pub fn r0hip_recursion_program_ctrl(program: *const R0HipRecursionProgram, d_ctrl: *mut *const u32) -> *const c_char;
+    /// r0hip_prove_recursion_keyed's seal with the control group's commitment taken from the handle
+    pub fn r0hip_prove_recursion_program(
+        program: *const R0HipRecursionProgram,
+        h_wom: *const u32,
+        n_wom: usize,
+        h_cycles: *const u32,
+        n_cycles: usize,
+        h_iops: *const u32,
+        n_iops: usize,
+        h_key: *const u32,
+        stream_id: u64,
+        h_seal: *mut u32,
+        seal_cap: usize,
+        seal_len: *mut usize,
+        h_mix_out: *mut u32,
+    ) -> *const c_char;
+    /// refused (nothing freed) while a proof or a queued worker job uses the handle
+    pub fn r0hip_recursion_program_destroy(program: *mut R0HipRecursionProgram) -> *const c_char;
     pub fn r0hip_prove_segments(
         circuit: *const c_char,
         suite: c_int,

@@ -13,6 +13,7 @@
 #include <cerrno>
 #include <cstdlib>
 #include <algorithm>
+#include <atomic>
 #include <cstring>
 #include <functional>
 #include <memory>
@@ -35,8 +36,10 @@ std::vector<uint32_t> prove_segment(const CircuitDef& c, int suite, uint32_t po2
                                     const uint32_t* data, const uint32_t* accum, uint32_t* global,
                                     bool write_version, uint32_t version, std::vector<uint32_t>* mix_out,
                                     const UploadGate* uploads = nullptr, const AccumStep* acc = nullptr,
-                                    GroupWork* code_early = nullptr);
+                                    GroupWork* code_early = nullptr, const CachedGroup* code_cached = nullptr);
 GroupWork commit_group_side(int k, int suite, const uint32_t* witness, size_t cols, size_t po2);
+std::vector<uint32_t> commit_group_keep(hipStream_t s, int suite, uint32_t* coeffs, uint32_t* evaluated, uint32_t* nodes,
+                                        const uint32_t* witness, size_t cols, size_t po2);
 std::string last_profile();
 }  // namespace r0
 
@@ -453,6 +456,26 @@ const char* r0hip_rv32im_witgen(uint32_t mode, const r0hip_raw_exec_buffers* buf
 
 }  // extern "C"
 
+// A recursion program resident on the device (r0hip_recursion_program_*): the control group
+// WitnessGenerator::new lays out (witgen.rs:57-67) and its commitment, which depend only on
+// (program, po2, suite), made once. The four buffers are dedicated allocations, read-only after
+// create; `top` is the host copy of the tree's root and top layers, control_id the root
+// (Program::compute_control_id, program.rs:74-104).
+struct r0hip_recursion_program {
+  static constexpr uint64_t kDestroyed = ~uint64_t(0);
+  int suite = 0;
+  uint32_t po2 = 0;
+  size_t code_rows = 0;
+  uint32_t* buf[4] = {nullptr, nullptr, nullptr, nullptr};  // ctrl, coeffs, evaluated, nodes
+  size_t bytes[4] = {0, 0, 0, 0};
+  uint32_t control_id[8] = {};
+  std::vector<uint32_t> top;
+  mutable std::atomic<uint64_t> uses{0};  // proofs running and worker jobs queued
+  ~r0hip_recursion_program() {
+    for (int i = 0; i < 4; i++) dev_free_dedicated(buf[i], bytes[i]);
+  }
+};
+
 namespace r0 {
 
 void check_injector(const uint32_t* index, size_t rows, const uint32_t* offsets, const uint32_t* values,
@@ -624,7 +647,8 @@ void check_injector(const uint32_t* index, size_t rows, const uint32_t* offsets,
 // `which` (0 the data group's, 1 the accum group's) on stream s.
 std::vector<uint32_t> prove_recursion(int suite, uint32_t po2, const uint32_t* d_ctrl, const uint32_t* h_wom,
                                       size_t n_wom, const uint32_t* h_cycles, size_t n_cycles, const uint32_t* h_iops,
-                                      size_t n_iops, const RecursionNoise& noise_fill, std::vector<uint32_t>* mix) {
+                                      size_t n_iops, const RecursionNoise& noise_fill, std::vector<uint32_t>* mix,
+                                      const CachedGroup* ctrl_cached) {
   const CircuitDef* c = find_circuit("recursion");
   R0_REQUIRE(c && d_ctrl, "r0hip_prove_recursion: null argument");
   R0_REQUIRE(po2 >= 11 && po2 <= 24, "r0hip_prove_recursion: po2 out of range (ZK rows need po2 >= 11)");
@@ -640,7 +664,8 @@ std::vector<uint32_t> prove_recursion(int suite, uint32_t po2, const uint32_t* d
   // its NTTs and hashes (throughput work) run on a side stream beside the generator, which is
   // bound by the latency of its exec runs and waits for the host; prove_segment joins
   GroupWork code_early;
-  const bool early = active_proof_streams() >= 2;
+  // (a cached control group has no commit left to move)
+  const bool early = !ctrl_cached && active_proof_streams() >= 2;
   if (early) code_early = commit_group_side(1, suite, d_ctrl, c->group_size(1), po2);
   HIP_OK(hipMemsetD32Async(data.p, 0xFFFFFFFFu, data.words, s));
   HIP_OK(hipMemsetD32Async(global.p, 0xFFFFFFFFu, global.words, s));
@@ -657,7 +682,7 @@ std::vector<uint32_t> prove_recursion(int suite, uint32_t po2, const uint32_t* d
   copy_elem_slice(s, accum.p, noise.p, accum_cols, kZk, 0, kZk, n - kZk, n);
   const AccumStep acc{accum.p, n_cycles};
   return prove_segment(*c, suite, po2, d_ctrl, data.p, nullptr, global.p, false, 0, mix, nullptr, &acc,
-                       early ? &code_early : nullptr);
+                       early ? &code_early : nullptr, ctrl_cached);
 }
 
 // The keyed noise of r0hip_prove_recursion_keyed: ChaCha20 under `key`, the data matrix with
@@ -672,6 +697,33 @@ RecursionNoise keyed_noise(const uint32_t* key, uint64_t stream_id) {
     fill_chacha20(s, out, count, k);
     explicit_bzero(&k, sizeof k);
   };
+}
+
+RecursionProgramShape recursion_program_shape(const r0hip_recursion_program* h) {
+  return RecursionProgramShape{h->suite, h->po2, h->code_rows, h->control_id};
+}
+void recursion_program_acquire(const r0hip_recursion_program* h) {
+  uint64_t v = h->uses.load(std::memory_order_relaxed);
+  do {
+    R0_REQUIRE(v != r0hip_recursion_program::kDestroyed, "recursion program: the handle is being destroyed");
+  } while (!h->uses.compare_exchange_weak(v, v + 1, std::memory_order_acquire, std::memory_order_relaxed));
+}
+void recursion_program_release(const r0hip_recursion_program* h) noexcept {
+  h->uses.fetch_sub(1, std::memory_order_release);
+}
+
+// r0hip_prove_recursion_program: prove_recursion with the control group and its commitment taken
+// from the handle (the caller holds a use count)
+std::vector<uint32_t> prove_recursion_program(const r0hip_recursion_program* h, const uint32_t* h_wom, size_t n_wom,
+                                              const uint32_t* h_cycles, size_t n_cycles, const uint32_t* h_iops,
+                                              size_t n_iops, const RecursionNoise& noise_fill,
+                                              std::vector<uint32_t>* mix) {
+  // witgen.rs:80: the trace has one cycle per program row
+  R0_REQUIRE(n_cycles == h->code_rows, "r0hip_prove_recursion_program: n_cycles " + std::to_string(n_cycles) +
+                                           " is not the program's code_rows " + std::to_string(h->code_rows));
+  const CachedGroup cg{h->buf[1], h->buf[2], h->buf[3], 23, h->top.data()};
+  return prove_recursion(h->suite, h->po2, h->buf[0], h_wom, n_wom, h_cycles, n_cycles, h_iops, n_iops, noise_fill, mix,
+                         &cg);
 }
 
 void os_random_key(uint32_t key[8]) {
@@ -809,6 +861,109 @@ const char* r0hip_prove_recursion_keyed(int suite, uint32_t po2, const uint32_t*
   });
   explicit_bzero(key, sizeof key);
   return err;
+}
+
+const char* r0hip_recursion_program_create(r0hip_recursion_program** out, int suite, uint32_t po2,
+                                           const uint32_t* h_code, size_t n_words, int form) {
+  return wrap([&] {
+    // every refusal on the host, before any device call
+    const std::string who = "r0hip_recursion_program_create: ";
+    R0_REQUIRE(out, who + "out is NULL");
+    *out = nullptr;
+    R0_REQUIRE(h_code, who + "h_code is NULL");
+    R0_REQUIRE(suite >= 0 && suite <= 2, who + "suite " + std::to_string(suite) + " is not a hash suite (0..2)");
+    R0_REQUIRE(form == R0HIP_CODE_ENCODED || form == R0HIP_CODE_MONTGOMERY,
+               who + "form " + std::to_string(form) + " is neither R0HIP_CODE_ENCODED nor R0HIP_CODE_MONTGOMERY");
+    R0_REQUIRE(po2 >= 11 && po2 <= 24, who + "po2 " + std::to_string(po2) + " outside 11..24 (the ZK rows need po2 >= 11)");
+    R0_REQUIRE(n_words != 0, who + "n_words is 0");
+    R0_REQUIRE(n_words % 23 == 0, who + "n_words " + std::to_string(n_words) + " is not a multiple of 23 (words per row)");
+    const size_t n = size_t(1) << po2, rows = n_words / 23;
+    R0_REQUIRE(rows <= n - 1024, who + "n_words gives " + std::to_string(rows) + " rows, above 2^po2 - ZK_CYCLES = " +
+                                     std::to_string(n - 1024));
+    if (form == R0HIP_CODE_MONTGOMERY)
+      for (size_t i = 0; i < n_words; i++)
+        R0_REQUIRE(h_code[i] < kP, who + "h_code[" + std::to_string(i) + "] = " + std::to_string(h_code[i]) +
+                                       " is not a canonical Montgomery word (>= p)");
+    auto h = std::make_unique<r0hip_recursion_program>();
+    h->suite = suite;
+    h->po2 = po2;
+    h->code_rows = rows;
+    const size_t words[4] = {23 * n, 23 * n, 23 * n * 4, n * 4 * 2 * 8};
+    for (int i = 0; i < 4; i++) {
+      h->buf[i] = static_cast<uint32_t*>(dev_alloc_dedicated(words[i] * 4));
+      h->bytes[i] = words[i] * 4;
+    }
+    hipStream_t s = stream();
+    stage_reset();
+    DevBuf code(n_words);
+    upload(code.p, h_code, n_words * 4);
+    recursion_program_expand(s, h->buf[0], code.p, n_words, po2, form);
+    h->top = commit_group_keep(s, suite, h->buf[1], h->buf[2], h->buf[3], h->buf[0], 23, po2);
+    memcpy(h->control_id, h->top.data(), 32);
+    *out = h.release();
+  });
+}
+
+const char* r0hip_recursion_program_info(const r0hip_recursion_program* program, int* suite, uint32_t* po2,
+                                         size_t* code_rows, uint32_t control_id[8], uint64_t* device_bytes) {
+  return wrap_nosync([&] {
+    R0_REQUIRE(program, "r0hip_recursion_program_info: program is NULL");
+    if (suite) *suite = program->suite;
+    if (po2) *po2 = program->po2;
+    if (code_rows) *code_rows = program->code_rows;
+    if (control_id) memcpy(control_id, program->control_id, 32);
+    if (device_bytes) *device_bytes = program->bytes[0] + program->bytes[1] + program->bytes[2] + program->bytes[3];
+  });
+}
+
+const char* r0hip_recursion_program_ctrl(const r0hip_recursion_program* program, const uint32_t** d_ctrl) {
+  return wrap_nosync([&] {
+    R0_REQUIRE(program, "r0hip_recursion_program_ctrl: program is NULL");
+    R0_REQUIRE(d_ctrl, "r0hip_recursion_program_ctrl: d_ctrl is NULL");
+    *d_ctrl = program->buf[0];
+  });
+}
+
+const char* r0hip_prove_recursion_program(const r0hip_recursion_program* program, const uint32_t* h_wom, size_t n_wom,
+                                          const uint32_t* h_cycles, size_t n_cycles, const uint32_t* h_iops,
+                                          size_t n_iops, const uint32_t* h_key, uint64_t stream_id, uint32_t* h_seal,
+                                          size_t seal_cap, size_t* seal_len, uint32_t* h_mix_out) {
+  uint32_t key[8];
+  bool held = false;
+  const char* err = wrap([&] {
+    const std::string who = "r0hip_prove_recursion_program: ";
+    R0_REQUIRE(program, who + "program is NULL");
+    R0_REQUIRE(h_wom || !n_wom, who + "h_wom is NULL with n_wom " + std::to_string(n_wom));
+    R0_REQUIRE(h_cycles || !n_cycles, who + "h_cycles is NULL with n_cycles " + std::to_string(n_cycles));
+    R0_REQUIRE(h_iops || !n_iops, who + "h_iops is NULL with n_iops " + std::to_string(n_iops));
+    R0_REQUIRE(!seal_cap || h_seal, who + "h_seal is NULL with seal_cap " + std::to_string(seal_cap));
+    R0_REQUIRE(n_cycles == program->code_rows, who + "n_cycles " + std::to_string(n_cycles) +
+                                                   " is not the program's code_rows " +
+                                                   std::to_string(program->code_rows));
+    recursion_program_acquire(program);
+    held = true;
+    if (h_key) memcpy(key, h_key, sizeof key);
+    else os_random_key(key);
+    std::vector<uint32_t> mix;
+    auto seal = prove_recursion_program(program, h_wom, n_wom, h_cycles, n_cycles, h_iops, n_iops,
+                                        keyed_noise(key, stream_id), &mix);
+    seal_out(seal, mix, h_seal, seal_cap, seal_len, h_mix_out);
+  });
+  // wrap has drained this thread's stream (on an error too): nothing of the proof reads the handle
+  if (held) recursion_program_release(program);
+  explicit_bzero(key, sizeof key);
+  return err;
+}
+
+const char* r0hip_recursion_program_destroy(r0hip_recursion_program* program) {
+  return wrap([&] {
+    R0_REQUIRE(program, "r0hip_recursion_program_destroy: program is NULL");
+    uint64_t idle = 0;
+    R0_REQUIRE(program->uses.compare_exchange_strong(idle, r0hip_recursion_program::kDestroyed),
+               "r0hip_recursion_program_destroy: program is in use by " + std::to_string(idle) +
+                   " proofs or queued worker jobs; nothing was freed");
+    delete program;
+  });
 }
 
 const char* r0hip_fill_chacha20(uint32_t* d_out, size_t count, const uint32_t* h_key, const uint32_t* h_nonce) {

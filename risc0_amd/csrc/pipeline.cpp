@@ -39,7 +39,7 @@ std::vector<uint32_t> prove_segment(const CircuitDef& c, int suite, uint32_t po2
                                     const uint32_t* data, const uint32_t* accum, uint32_t* global,
                                     bool write_version, uint32_t version, std::vector<uint32_t>* mix_out,
                                     const UploadGate* uploads, const AccumStep* acc = nullptr,
-                                    GroupWork* code_early = nullptr);
+                                    GroupWork* code_early = nullptr, const CachedGroup* code_cached = nullptr);
 // api.cpp: rv32im prove_core from a preflight trace, and the host check of an injector
 std::vector<uint32_t> prove_trace(int suite, uint32_t po2, uint32_t mode, const uint32_t* global_in,
                                   const uint32_t* inj_index, size_t inj_rows, const uint32_t* inj_offsets,
@@ -398,7 +398,10 @@ const char* prove_trace_jobs(int suite, uint32_t po2, r0hip_trace_job* jobs, siz
 // seals go to the verifier thread (or straight to the finished list) and r0hip_worker_wait
 // hands them out in completion order. The trace buffers of a set are sized for max_po2; the
 // injector, transaction, BigInt and control-group buffers grow on the uploader thread while the
-// set is free, before the set is handed to a prover (which reads their pointers then).
+// set is free, before the set is handed to a prover (which reads their pointers then). A job of
+// kind R0HIP_JOB_RECURSION_PROGRAM stages nothing and grows nothing: its control group and the
+// group's commitment live in the caller's handle, on which the job holds a use count from
+// submit to finish().
 struct WorkerSet : TraceSet {
   DevBuf ctrl;  // recursion jobs: the control group (allocated at the set's first one)
   r0hip_worker_job* wjob = nullptr;
@@ -410,6 +413,11 @@ struct WorkerSet : TraceSet {
   BacksInfo backs_info;
   std::vector<r0hip_bigint_back> backs_bigint;
 };
+
+// a job of kind R0HIP_JOB_RECURSION_PROGRAM is the first member of an r0hip_worker_program_job
+inline const r0hip_recursion_program* job_program(const r0hip_worker_job* j) {
+  return reinterpret_cast<const r0hip_worker_program_job*>(j)->program;
+}
 
 struct WorkerImpl {
   uint32_t max_po2 = 0;
@@ -432,6 +440,9 @@ struct WorkerImpl {
   std::vector<std::thread> provers;
 
   void finish(r0hip_worker_job* j) {
+    // the job's proof has drained (or never ran): its hold on a resident program ends here,
+    // before r0hip_worker_wait can hand the job back
+    if (j->kind == R0HIP_JOB_RECURSION_PROGRAM) recursion_program_release(job_program(j));
     {
       std::lock_guard<std::mutex> lk(mu);
       finished.push_back(j);
@@ -453,6 +464,7 @@ struct WorkerImpl {
       if (b.ctrl.words < 23 * n) b.ctrl = DevBuf(23 * n);
       return;
     }
+    if (j.kind == R0HIP_JOB_RECURSION_PROGRAM) return;  // the control group lives in the handle
     const r0hip_trace_input& t = j.trace;
     if (j.kind == R0HIP_JOB_RV32IM_BACKS) {  // checked at submit: at most n records, n_words below 2^32
       if (j.backs->n > b.cap_recs) {
@@ -527,6 +539,8 @@ struct WorkerImpl {
             stage_reset();
             upload_async(b.ctrl.p, j->recursion.h_ctrl, 23 * n * 4);
             HIP_OK(hipEventRecord(b.ev, stream()));
+          } else if (j->kind == R0HIP_JOB_RECURSION_PROGRAM) {
+            // nothing to stage: the prover reads the handle and the job's host arrays
           } else if (j->kind == R0HIP_JOB_RV32IM_BACKS) {
             // the records were checked at submit; no index, offsets or values are staged
             const r0hip_raw_preflight_trace& pf = j->trace.preflight;
@@ -580,6 +594,15 @@ struct WorkerImpl {
           const r0hip_recursion_input& in = j->recursion;
           seal = prove_recursion(j->suite, j->po2, b.ctrl.p, in.h_wom, in.n_wom, in.h_cycles, in.n_cycles, in.h_iops,
                                  in.n_iops, keyed_noise(key, j->ticket), &mix);
+        } else if (j->kind == R0HIP_JOB_RECURSION_PROGRAM) {
+          b.wait_landed();  // at once: the uploader stages nothing for this kind
+          {
+            std::lock_guard<std::mutex> lk(b.mu);
+            if (j->error) throw std::runtime_error(j->error);
+          }
+          const r0hip_recursion_input& in = j->recursion;
+          seal = prove_recursion_program(job_program(j), in.h_wom, in.n_wom, in.h_cycles, in.n_cycles, in.h_iops,
+                                         in.n_iops, keyed_noise(key, j->ticket), &mix);
         } else if (j->kind == R0HIP_JOB_RV32IM_BACKS) {
           // the set's counts and BigInt records were written by the uploader before the hand-over
           // (grow); the record and word counts are the caller's, checked at submit
@@ -623,12 +646,18 @@ struct WorkerImpl {
       }
       r0hip_worker_job* j = item.first;
       if (!j) return;
-      const bool rec = j->kind == R0HIP_JOB_RECURSION;
+      const bool rec = j->kind == R0HIP_JOB_RECURSION || j->kind == R0HIP_JOB_RECURSION_PROGRAM;
       const auto t0 = std::chrono::steady_clock::now();
       uint32_t got = 0;
+      const uint32_t* roots = rec ? j->recursion.h_code_roots : nullptr;
+      size_t n_roots = rec ? j->recursion.n_code_roots : 0;
+      if (j->kind == R0HIP_JOB_RECURSION_PROGRAM && n_roots == 0) {
+        // no allow-list given: the seal must carry the handle's own control id
+        roots = recursion_program_shape(job_program(j)).control_id;
+        n_roots = 1;
+      }
       const char* err = r0hip_verify_seal(rec ? "recursion" : "rv32im", j->suite, item.second.data(),
-                                          item.second.size(), rec ? j->recursion.h_code_roots : nullptr,
-                                          rec ? j->recursion.n_code_roots : 0, nullptr, &got);
+                                          item.second.size(), roots, n_roots, nullptr, &got);
       j->verify_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
       if (!err && got != j->po2) err = dup_msg("the seal is of another segment size");
       if (err) {
@@ -939,7 +968,7 @@ extern "C" const char* r0hip_worker_submit(r0hip_worker* w, r0hip_worker_job* jo
     R0_REQUIRE(w && job, "r0hip_worker_submit: null argument");
     WorkerImpl& m = w->impl;
     R0_REQUIRE(job->kind == R0HIP_JOB_RV32IM_TRACE || job->kind == R0HIP_JOB_RECURSION ||
-                   job->kind == R0HIP_JOB_RV32IM_BACKS,
+                   job->kind == R0HIP_JOB_RV32IM_BACKS || job->kind == R0HIP_JOB_RECURSION_PROGRAM,
                "r0hip_worker_submit: unknown job kind");
     BacksInfo info;
     R0_REQUIRE(job->suite >= 0 && job->suite <= 2, "r0hip_worker_submit: unknown hash suite");
@@ -954,6 +983,19 @@ extern "C" const char* r0hip_worker_submit(r0hip_worker* w, r0hip_worker_job* jo
       R0_REQUIRE(in.h_ctrl && (in.h_wom || !in.n_wom) && (in.h_cycles || !in.n_cycles) && (in.h_iops || !in.n_iops) &&
                      (in.h_code_roots || !in.n_code_roots),
                  "r0hip_worker_submit: recursion job: null argument");
+    } else if (job->kind == R0HIP_JOB_RECURSION_PROGRAM) {
+      const r0hip_recursion_input& in = job->recursion;
+      R0_REQUIRE(job_program(job), "r0hip_worker_submit: recursion program job: program is NULL");
+      const RecursionProgramShape sh = recursion_program_shape(job_program(job));
+      R0_REQUIRE(sh.suite == job->suite, "r0hip_worker_submit: the program's suite " + std::to_string(sh.suite) +
+                                             " is not the job's suite " + std::to_string(job->suite));
+      R0_REQUIRE(sh.po2 == job->po2, "r0hip_worker_submit: the program's po2 " + std::to_string(sh.po2) +
+                                         " is not the job's po2 " + std::to_string(job->po2));
+      R0_REQUIRE(in.n_cycles == sh.code_rows, "r0hip_worker_submit: n_cycles " + std::to_string(in.n_cycles) +
+                                                  " is not the program's code_rows " + std::to_string(sh.code_rows));
+      R0_REQUIRE((in.h_wom || !in.n_wom) && (in.h_cycles || !in.n_cycles) && (in.h_iops || !in.n_iops) &&
+                     (in.h_code_roots || !in.n_code_roots),
+                 "r0hip_worker_submit: recursion program job: null argument");
     } else if (job->kind == R0HIP_JOB_RV32IM_BACKS) {
       R0_REQUIRE(job->po2 >= 2, "r0hip_worker_submit: po2 out of range");
       check_backs_trace(job->trace, "r0hip_worker_submit");
@@ -975,6 +1017,8 @@ extern "C" const char* r0hip_worker_submit(r0hip_worker* w, r0hip_worker_job* jo
     {
       std::lock_guard<std::mutex> lk(m.mu);
       R0_REQUIRE(!m.stopping, "r0hip_worker_submit: the worker is shutting down");
+      // the last thing that can refuse: a queued job holds the program until finish()
+      if (job->kind == R0HIP_JOB_RECURSION_PROGRAM) recursion_program_acquire(job_program(job));
       job->ticket = m.next_ticket++;
       m.outstanding++;
       m.fifo.emplace_back(job, info);

@@ -100,23 +100,31 @@ struct MerkleTree {
     }
     finish(std::move(leaf_nodes), m, r, c);
   }
-  void finish(DevBuf n, const uint32_t* m, size_t r, size_t c) {
-    rows = r;
-    cols = c;
-    matrix = m;
-    nodes = std::move(n);
-    layers = log2_exact(rows);
+  static size_t top_size_of(size_t r) {
+    const size_t layers = log2_exact(r);
     size_t top_layer = 0;
     for (size_t i = 1; i < layers; i++) {
       if ((size_t(1) << i) > QUERIES) break;
       top_layer = i;
     }
-    top_size = size_t(1) << top_layer;
+    return size_t(1) << top_layer;
+  }
+  void finish(DevBuf n, const uint32_t* m, size_t r, size_t c) {
     // root (node 1) .. end of the top layer in one copy
-    std::vector<uint32_t> h((2 * top_size - 1) * 8);
-    d2h(h.data(), nodes.p + 8, h.size() * 4);
-    memcpy(root.w, h.data(), 32);
-    top.assign(h.begin() + (top_size - 1) * 8, h.end());
+    std::vector<uint32_t> h((2 * top_size_of(r) - 1) * 8);
+    d2h(h.data(), n.p + 8, h.size() * 4);
+    finish_from(std::move(n), m, r, c, h.data());
+  }
+  // the same from a host copy `h` of those words (a CachedGroup's): nothing is read back
+  void finish_from(DevBuf n, const uint32_t* m, size_t r, size_t c, const uint32_t* h) {
+    rows = r;
+    cols = c;
+    matrix = m;
+    nodes = std::move(n);
+    layers = log2_exact(rows);
+    top_size = top_size_of(rows);
+    memcpy(root.w, h, 32);
+    top.assign(h + (top_size - 1) * 8, h + (2 * top_size - 1) * 8);
   }
   void commit(WriteIOP& iop) const {
     iop.write(top.data(), top.size());
@@ -149,6 +157,14 @@ struct PolyGroup {
   PolyGroup(GroupWork w, size_t po2)
       : coeffs(std::move(w.coeffs)), count(w.count), bitrev(coeffs_stay_bitrev(po2)), evaluated(std::move(w.evaluated)) {
     tree.finish(std::move(w.nodes), evaluated.p, (size_t(1) << po2) * INV_RATE, count);
+  }
+  // a group committed earlier and kept (CachedGroup): every buffer is borrowed, so nothing here
+  // frees or writes it, and the tree top comes from the host copy
+  PolyGroup(const CachedGroup& g, size_t po2) : count(g.count), bitrev(coeffs_stay_bitrev(po2)) {
+    const size_t size = size_t(1) << po2, domain = size * INV_RATE;
+    coeffs = DevBuf::borrow(g.coeffs, count * size);
+    evaluated = DevBuf::borrow(g.evaluated, count * domain);
+    tree.finish_from(DevBuf::borrow(g.nodes, domain * 2 * 8), evaluated.p, domain, count, g.top);
   }
   // coefficients (natural order below po2 12), evaluations and leaf digests already made
   // chunk by chunk
@@ -228,14 +244,29 @@ GroupWork group_buffers(size_t cols, size_t po2) {
   w.nodes = DevBuf(domain * 2 * 8);
   return w;
 }
-void commit_group_queue(hipStream_t s, int suite, GroupWork& w, const uint32_t* witness, size_t po2) {
+void commit_group_queue(hipStream_t s, int suite, uint32_t* coeffs, uint32_t* evaluated, uint32_t* nodes, size_t count,
+                        const uint32_t* witness, size_t po2) {
   const size_t domain = (size_t(1) << po2) * INV_RATE;
-  ntt_interpolate_from(s, w.coeffs.p, witness, w.count, uint32_t(po2), true);
-  ntt_evaluate(s, w.evaluated.p, w.coeffs.p, w.count, uint32_t(po2 + 2), 2);
-  if (!coeffs_stay_bitrev(po2)) bit_reverse(s, w.coeffs.p, w.count, uint32_t(po2));
-  merkle_tree(s, suite, w.nodes.p, w.evaluated.p, domain, w.count);
+  ntt_interpolate_from(s, coeffs, witness, count, uint32_t(po2), true);
+  ntt_evaluate(s, evaluated, coeffs, count, uint32_t(po2 + 2), 2);
+  if (!coeffs_stay_bitrev(po2)) bit_reverse(s, coeffs, count, uint32_t(po2));
+  merkle_tree(s, suite, nodes, evaluated, domain, count);
+}
+void commit_group_queue(hipStream_t s, int suite, GroupWork& w, const uint32_t* witness, size_t po2) {
+  commit_group_queue(s, suite, w.coeffs.p, w.evaluated.p, w.nodes.p, w.count, witness, po2);
 }
 }  // namespace
+
+// commit_group's device half into buffers the caller owns (cols * 2^po2, cols * 2^(po2+2) and
+// 16 * 2^(po2+2) words), then the host copy of the tree's root and top layers a CachedGroup
+// carries; this thread's stream is drained on return.
+std::vector<uint32_t> commit_group_keep(hipStream_t s, int suite, uint32_t* coeffs, uint32_t* evaluated, uint32_t* nodes,
+                                        const uint32_t* witness, size_t cols, size_t po2) {
+  commit_group_queue(s, suite, coeffs, evaluated, nodes, cols, witness, po2);
+  std::vector<uint32_t> h((2 * MerkleTree::top_size_of((size_t(1) << po2) * INV_RATE) - 1) * 8);
+  d2h(h.data(), nodes + 8, h.size() * 4);
+  return h;
+}
 
 // commit_group's device half on stream s: interpolate (zk shift fused), evaluate on the 4x
 // domain, row hashes and tree layers, the kernels of commit_group in its order. Nothing is
@@ -398,6 +429,14 @@ struct Prover {
   void commit_group_finish(size_t g, GroupWork w) {
     Span span("commit_group");
     groups[g].reset(new PolyGroup(std::move(w), po2));
+    groups[g]->tree.commit(iop);
+  }
+  // commit_group for a group committed before this proof: no device work, the root enters the
+  // transcript where tree.commit puts it
+  void commit_group_cached(size_t g, const CachedGroup& cg) {
+    Span span("commit_group");
+    R0_REQUIRE(cg.count == c.group_size(g), "cached group has another column count");
+    groups[g].reset(new PolyGroup(cg, po2));
     groups[g]->tree.commit(iop);
   }
 
@@ -645,8 +684,10 @@ std::string last_profile() { return g_last_profile; }
 std::vector<uint32_t> prove_segment(const CircuitDef& c, int suite, uint32_t po2, const uint32_t* code,
                                     const uint32_t* data, const uint32_t* accum, uint32_t* global,
                                     bool write_version, uint32_t version, std::vector<uint32_t>* mix_out,
-                                    const UploadGate* uploads, const AccumStep* acc, GroupWork* code_early) {
+                                    const UploadGate* uploads, const AccumStep* acc, GroupWork* code_early,
+                                    const CachedGroup* code_cached) {
   R0_REQUIRE(suite >= 0 && suite <= 2, "unknown hash suite");
+  R0_REQUIRE(!code_cached || (!code_early && !uploads), "prove_segment: a cached code group with one in flight");
   R0_REQUIRE(!acc || (acc->accum && !accum), "prove_segment: give the accum group or an accumulation, not both");
   R0_REQUIRE(po2 >= 2 && po2 <= 24, "po2 out of range");
   Span span("prove_core");
@@ -691,7 +732,15 @@ std::vector<uint32_t> prove_segment(const CircuitDef& c, int suite, uint32_t po2
   // (code_early) or here, beside the data group's on the main stream. The roots are read and
   // hashed into the transcript in the reference's order, code then data, and the side stream is
   // joined before anything reads the code group's buffers.
-  if (code_early || (!uploads && active_proof_streams() >= 2)) {
+  // code_cached (a recursion program handle): the code group was committed when the handle was
+  // made; there is no code commit to queue or to fork, whatever r0hip_set_proof_streams says,
+  // and the data group is committed as at n = 1.
+  if (code_cached) {
+    p.commit_group_cached(1, *code_cached);
+    prof.mark("commit_code");
+    commit(2, 1, data);
+    prof.mark("commit_data");
+  } else if (code_early || (!uploads && active_proof_streams() >= 2)) {
     GroupWork cw = code_early ? std::move(*code_early) : commit_group_side(1, suite, code, c.group_size(1), po2);
     GroupWork dw = commit_group_device(s, suite, data, c.group_size(2), po2);
     join(1);

@@ -117,6 +117,53 @@ __global__ __launch_bounds__(kT) void inject_backs_kernel(uint32_t* data, uint32
   for (int k = 0; k < 5; k++) data[uint64_t(k) * steps + c - 1] = v[k];
 }
 
+// Program.code (row-major, 23 words per row) into the control group (column-major): workgroup b
+// stages rows [b * kT, (b + 1) * kT) in LDS with coalesced loads (a tile starts 16-byte aligned:
+// kT * 23 * 4 bytes is a multiple of 16 and so is the base of `code`, checked by the launcher;
+// whole uint4 loads while four words remain, single words at the tail), then lane t writes
+// row b * kT + t of each column: 23 runs of kT consecutive words. A lane's LDS reads walk a row
+// at stride 23 words across lanes, which is odd, so no two lanes of a group share a bank. Words
+// at or past n_words are never read and arrive as zero: the padding rows (and whole padding
+// tiles, which load nothing) are written by this launch. `n` (2^po2) is a multiple of kT.
+constexpr uint32_t kCodeCols = 23, kTileWords = kT * kCodeCols;
+static_assert(kTileWords % 4 == 0, "a tile is a whole number of uint4");
+template <int FORM>
+__global__ __launch_bounds__(kT) void program_expand_kernel(uint32_t* ctrl, const uint32_t* code, uint64_t n_words,
+                                                           uint32_t n) {
+  __shared__ uint32_t tile[kTileWords];
+  const uint64_t base = uint64_t(blockIdx.x) * kTileWords;
+  const uint64_t left = base < n_words ? n_words - base : 0;  // words of this tile that exist
+  auto elem = [](uint32_t x) {
+    if (FORM != 0) return x;
+    x = umin(x, x - kP);  // x < 2^32 < 3p: two conditional subtractions give x mod p
+    x = umin(x, x - kP);
+    return fp_mul(kR2, x);  // Elem::from
+  };
+  if (left != 0) {
+    for (uint32_t q = threadIdx.x; q < kTileWords / 4; q += kT) {
+      const uint32_t w = 4 * q;
+      uint4 v = make_uint4(0u, 0u, 0u, 0u);
+      if (w + 4 <= left) {
+        v = *reinterpret_cast<const uint4*>(code + base + w);
+      } else {
+        if (w < left) v.x = code[base + w];
+        if (w + 1 < left) v.y = code[base + w + 1];
+        if (w + 2 < left) v.z = code[base + w + 2];
+      }
+      tile[w] = elem(v.x);
+      tile[w + 1] = elem(v.y);
+      tile[w + 2] = elem(v.z);
+      tile[w + 3] = elem(v.w);
+    }
+    __syncthreads();
+  }
+  const uint32_t row = blockIdx.x * kT + threadIdx.x;
+  if (row >= n) return;
+#pragma unroll
+  for (uint32_t c = 0; c < kCodeCols; c++)
+    ctrl[uint64_t(c) * n + row] = left != 0 ? tile[threadIdx.x * kCodeCols + c] : 0u;
+}
+
 std::string witgen_error(uint32_t code, uint32_t cycle) {
   using namespace rwg;
   const std::string at = " (cycle " + std::to_string(cycle) + ")";
@@ -130,6 +177,21 @@ std::string witgen_error(uint32_t code, uint32_t cycle) {
 }
 
 }  // namespace
+
+void recursion_program_expand(hipStream_t s, uint32_t* ctrl, const uint32_t* code, size_t n_words, uint32_t po2,
+                              int form) {
+  R0_REQUIRE(po2 >= 11 && po2 <= 24, "recursion_program_expand: po2 out of range");
+  const size_t n = size_t(1) << po2;
+  R0_REQUIRE(ctrl && code && n_words % kCodeCols == 0 && n_words / kCodeCols <= n,
+             "recursion_program_expand: the program does not fit the control group");
+  R0_REQUIRE(form == 0 || form == 1, "recursion_program_expand: unknown form");
+  R0_REQUIRE(reinterpret_cast<uintptr_t>(code) % 16 == 0, "recursion_program_expand: code is not 16-byte aligned");
+  KScope ks("recursion_program_expand", 4.0 * double(n_words) + 4.0 * kCodeCols * double(n));
+  const dim3 grid(unsigned(n / kT)), block(kT);
+  if (form == 0) hipLaunchKernelGGL(program_expand_kernel<0>, grid, block, 0, s, ctrl, code, uint64_t(n_words), uint32_t(n));
+  else hipLaunchKernelGGL(program_expand_kernel<1>, grid, block, 0, s, ctrl, code, uint64_t(n_words), uint32_t(n));
+  HIP_OK(hipGetLastError());
+}
 
 void recursion_witgen(hipStream_t s, const uint32_t* ctrl, uint32_t* data, uint32_t* global, size_t total_cycles,
                       const uint32_t* h_wom, size_t n_wom, const uint32_t* h_cycles, size_t ncycles,

@@ -606,6 +606,23 @@ void dev_free(void* p) {
   t_ctx.pool.emplace(bytes, p);  // reused only by this thread, i.e. on this stream
 }
 
+void* dev_alloc_dedicated(size_t bytes) {
+  ensure_init();
+  void* p = nullptr;
+  if (counted_malloc(&p, bytes) != hipSuccess) {
+    dev_trim();
+    HIP_OK(counted_malloc(&p, bytes));
+  }
+  live_add(bytes);
+  return p;
+}
+
+void dev_free_dedicated(void* p, size_t bytes) {
+  if (!p) return;
+  live_sub(bytes);
+  counted_free(p, bytes);  // hipFree waits for the device: no kernel still reads the block
+}
+
 // ---- page-locked host memory (r0hip_host_alloc / r0hip_host_free) ----------------
 // Freed blocks stay page-locked in a size-keyed list for the next request instead of going
 // back through hipHostFree. Unpinning host memory is not free for the device: after the

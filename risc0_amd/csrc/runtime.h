@@ -14,6 +14,7 @@
 #include "bb31.h"
 
 struct r0hip_bigint_back;  // include/r0hip.h
+struct r0hip_recursion_program;
 
 #define HIP_OK(expr)                                                                          \
   do {                                                                                        \
@@ -318,9 +319,33 @@ void os_random_key(uint32_t key[8]);
 // (8 words, read at each fill) with nonce {which, lo32(stream_id), hi32(stream_id)}.
 using RecursionNoise = std::function<void(hipStream_t s, uint32_t* out, size_t count, uint32_t which)>;
 RecursionNoise keyed_noise(const uint32_t* key, uint64_t stream_id);
+// ctrl_cached (devmem.h): the control group's commitment, made earlier from d_ctrl and kept
+struct CachedGroup;
 std::vector<uint32_t> prove_recursion(int suite, uint32_t po2, const uint32_t* d_ctrl, const uint32_t* h_wom,
                                       size_t n_wom, const uint32_t* h_cycles, size_t n_cycles, const uint32_t* h_iops,
-                                      size_t n_iops, const RecursionNoise& noise_fill, std::vector<uint32_t>* mix);
+                                      size_t n_iops, const RecursionNoise& noise_fill, std::vector<uint32_t>* mix,
+                                      const CachedGroup* ctrl_cached = nullptr);
+// A recursion program handle (r0hip_recursion_program, api.cpp) for the worker: its shape, a use
+// count taken per proof or queued job (destroy refuses while one is held), and the proof of
+// r0hip_prove_recursion_program on the calling thread's stream.
+struct RecursionProgramShape {
+  int suite;
+  uint32_t po2;
+  size_t code_rows;
+  const uint32_t* control_id;  // 8 words
+};
+RecursionProgramShape recursion_program_shape(const r0hip_recursion_program* h);
+void recursion_program_acquire(const r0hip_recursion_program* h);
+void recursion_program_release(const r0hip_recursion_program* h) noexcept;
+std::vector<uint32_t> prove_recursion_program(const r0hip_recursion_program* h, const uint32_t* h_wom, size_t n_wom,
+                                              const uint32_t* h_cycles, size_t n_cycles, const uint32_t* h_iops,
+                                              size_t n_iops, const RecursionNoise& noise_fill,
+                                              std::vector<uint32_t>* mix);
+// Program.code (rows x 23 words, row-major, on the device) into the control group: 23 columns
+// of 2^po2 words, rows from n_words / 23 on zero, every word of the group written by this launch.
+// form 0: each word x becomes Elem::from(x) (the Montgomery word of x mod p); form 1: copied.
+void recursion_program_expand(hipStream_t s, uint32_t* ctrl, const uint32_t* code, size_t n_words, uint32_t po2,
+                              int form);
 void rv32im_accum_finalize(hipStream_t s, uint32_t* accum, size_t rows, size_t cols, size_t split, size_t last);
 void rv32im_accum(hipStream_t s, const uint32_t* data, uint32_t* accum, const uint32_t* global,
                   const uint32_t* mix, size_t rows, size_t cols, size_t last);

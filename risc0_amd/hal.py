@@ -113,6 +113,13 @@ def _declare(L):
                                   C.POINTER(sz), u32p],
         "r0hip_prove_recursion_keyed": [C.c_int, C.c_uint32, vp, u32p, sz, u32p, sz, u32p, sz, u32p, C.c_uint64, u32p,
                                         sz, C.POINTER(sz), u32p],
+        "r0hip_recursion_program_create": [C.POINTER(vp), C.c_int, C.c_uint32, u32p, sz, C.c_int],
+        "r0hip_recursion_program_info": [vp, C.POINTER(C.c_int), C.POINTER(C.c_uint32), C.POINTER(sz), u32p,
+                                         C.POINTER(C.c_uint64)],
+        "r0hip_recursion_program_ctrl": [vp, C.POINTER(vp)],
+        "r0hip_prove_recursion_program": [vp, u32p, sz, u32p, sz, u32p, sz, u32p, C.c_uint64, u32p, sz, C.POINTER(sz),
+                                          u32p],
+        "r0hip_recursion_program_destroy": [vp],
         "r0hip_worker_create": [C.POINTER(vp), C.c_uint32, C.c_uint32, C.c_int, u32p],
         "r0hip_worker_submit": [vp, vp],
         "r0hip_worker_wait": [vp, C.POINTER(vp), C.c_int64],
@@ -596,6 +603,92 @@ def prove_recursion_keyed(hal, po2, ctrl, wom, cycles, iops, key, stream_id, sea
     return seal[: n.value].copy(), mix
 
 
+CODE_ENCODED, CODE_MONTGOMERY = 0, 1
+
+
+class RecursionProgram:
+    """A recursion program resident on the device (r0hip_recursion_program_*): the control group
+    and its commitment, made once from the program's rows and reused by every proof.
+
+        with RecursionProgram.create(hal, po2, program.encoded()) as prog:
+            suite, po2, rows, control_id, device_bytes = prog.info()
+            seal, mix = prog.prove(wom, cycles, iops, key, stream_id)
+
+    `code` is row-major, 23 words per row: plain integers as a .zkr holds them (CODE_ENCODED,
+    each word goes through Elem::from) or Program.code's Montgomery words (CODE_MONTGOMERY).
+    close() is refused while a proof or a queued worker job still uses the handle."""
+
+    def __init__(self, handle, suite):
+        self._h, self.suite = handle, suite
+
+    @classmethod
+    def create(cls, hal, po2, code, form=CODE_ENCODED, suite=None, n_words=None):
+        """n_words: the program's length when `code` is a longer array (default: all of it)"""
+        suite = hal.suite if suite is None else (SUITES[suite] if isinstance(suite, str) else int(suite))
+        c = np.ascontiguousarray(code, dtype=np.uint32).reshape(-1)
+        if n_words is not None and n_words > c.size:
+            raise R0HipError(f"n_words {n_words} is more than the {c.size} words given")
+        h = C.c_void_p()
+        check(lib().r0hip_recursion_program_create(C.byref(h), suite, po2, c.ctypes.data_as(u32p),
+                                                   c.size if n_words is None else n_words, form))
+        return cls(h, suite)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def _handle(self):
+        if self._h is None or not self._h.value:
+            raise R0HipError("the recursion program is closed")
+        return self._h
+
+    def info(self):
+        """(suite, po2, code_rows, control_id as 8 words, device_bytes)"""
+        suite, po2, rows, dev = C.c_int(), C.c_uint32(), C.c_size_t(), C.c_uint64()
+        cid = np.zeros(8, dtype=np.uint32)
+        check(lib().r0hip_recursion_program_info(self._handle(), C.byref(suite), C.byref(po2), C.byref(rows),
+                                                 cid.ctypes.data_as(u32p), C.byref(dev)))
+        return suite.value, po2.value, rows.value, cid, dev.value
+
+    def ctrl_ptr(self):
+        """device address of the control group (read-only; valid until close)"""
+        p = C.c_void_p()
+        check(lib().r0hip_recursion_program_ctrl(self._handle(), C.byref(p)))
+        return p.value
+
+    def ctrl(self):
+        """the control group read back: 23 x 2^po2 Montgomery words, column-major"""
+        _suite, po2, _rows, _cid, _dev = self.info()
+        out = np.zeros(23 << po2, dtype=np.uint32)
+        check(lib().r0hip_memcpy_d2h(out.ctypes.data, self.ctrl_ptr(), out.nbytes))
+        return out
+
+    def prove(self, wom, cycles, iops, key, stream_id, seal_cap=1 << 24):
+        """r0hip_prove_recursion_program: the seal and mix of prove_recursion_keyed on this
+        program's control group with the same key and stream_id"""
+        w, c, i = _trace(wom, cycles, iops)
+        k, kp = _key_words(key)
+        seal = np.zeros(seal_cap, dtype=np.uint32)
+        n = C.c_size_t(0)
+        mix = np.zeros(20, dtype=np.uint32)
+        check(lib().r0hip_prove_recursion_program(self._handle(), w.ctypes.data_as(u32p), w.size // 4,
+                                                  c.ctypes.data_as(u32p), c.size // 2, i.ctypes.data_as(u32p),
+                                                  i.size // 4, kp, stream_id, seal.ctypes.data_as(u32p), seal_cap,
+                                                  C.byref(n), mix.ctypes.data_as(u32p)))
+        return seal[: n.value].copy(), mix
+
+    def close(self):
+        """r0hip_recursion_program_destroy; raises (and keeps the handle) while it is in use"""
+        h = getattr(self, "_h", None)
+        if h is None or not h.value:
+            return
+        check(lib().r0hip_recursion_program_destroy(h))
+        self._h = None
+
+
 class RawBuffer(C.Structure):
     """struct r0hip_raw_buffer (RawBuffer, rv32im-sys/src/lib.rs:63-69)"""
     _fields_ = [("buf", C.c_void_p), ("rows", C.c_size_t), ("cols", C.c_size_t), ("checked", C.c_bool)]
@@ -893,7 +986,13 @@ class WorkerJobStruct(C.Structure):
                 ("prove_ms", C.c_double), ("ticket", C.c_uint64), ("backs", C.c_void_p)]
 
 
-JOB_RV32IM_TRACE, JOB_RECURSION, JOB_RV32IM_BACKS = 0, 1, 2
+class WorkerProgramJobStruct(C.Structure):
+    """struct r0hip_worker_program_job (include/r0hip.h): a kind-3 job, the job struct with the
+    resident program's handle appended; its `job` member is what submit takes"""
+    _fields_ = [("job", WorkerJobStruct), ("program", C.c_void_p)]
+
+
+JOB_RV32IM_TRACE, JOB_RECURSION, JOB_RV32IM_BACKS, JOB_RECURSION_PROGRAM = 0, 1, 2, 3
 
 
 class BacksJob:
@@ -1020,6 +1119,28 @@ class Worker:
                                        i.ctypes.data if i.size else None, i.size // 4,
                                        roots.ctypes.data if roots.size else None, roots.size // 8)
         return self._submit(job, 20, (ct, w, c, i, roots))
+
+    def submit_recursion_program(self, program, wom, cycles, iops, code_roots=None, po2=None, suite=None):
+        """queue one recursion proof from a RecursionProgram (kind R0HIP_JOB_RECURSION_PROGRAM):
+        no control group is staged. code_roots: the allow-list of its receipt check (default:
+        the program's own control id). po2 and suite default to the program's; a mismatch is
+        refused (R0HipError). Returns its ticket, which is also the stream_id of its ZK noise."""
+        w, c, i = _trace(wom, cycles, iops)
+        roots = np.ascontiguousarray(np.zeros(0, np.uint32) if code_roots is None else code_roots,
+                                     dtype=np.uint32).reshape(-1)
+        if roots.size % 8:
+            raise R0HipError("code_roots holds 8 words per root")
+        p_suite, p_po2 = program.info()[:2]
+        pj = WorkerProgramJobStruct()
+        pj.program = program._handle().value
+        job = pj.job  # a view of pj's first member: the address submit takes and wait returns
+        job.kind, job.po2 = JOB_RECURSION_PROGRAM, p_po2 if po2 is None else po2
+        job.suite = p_suite if suite is None else (SUITES[suite] if isinstance(suite, str) else int(suite))
+        job.recursion = RecursionInput(None, w.ctypes.data if w.size else None, w.size // 4,
+                                       c.ctypes.data if c.size else None, c.size // 2,
+                                       i.ctypes.data if i.size else None, i.size // 4,
+                                       roots.ctypes.data if roots.size else None, roots.size // 8)
+        return self._submit(job, 20, (pj, program, w, c, i, roots))
 
     def outstanding(self):
         """jobs submitted and not yet returned by wait()"""
