@@ -554,6 +554,79 @@ const char* r0hip_prove_recursion_program(const r0hip_recursion_program* program
                                           const uint32_t* h_cycles, size_t n_cycles, const uint32_t* h_iops,
                                           size_t n_iops, const uint32_t* h_key, uint64_t stream_id, uint32_t* h_seal,
                                           size_t seal_cap, size_t* seal_len, uint32_t* h_mix_out);
+/* ---- recursion proofs from a program and its input words (RecursionProver::prove(program,
+ * input), circuit/recursion/src/prove/mod.rs:165; the preflight, prove/preflight.rs:181-627) ----
+ * The entry points above take the preflight's arrays. These take what the reference calls
+ * `input` and run the preflight themselves, natively on the host (csrc/recursion_preflight.h).
+ * Covered: the micro ops CONST .. EXTRACT, the macro ops nop, wom_init, wom_fini, set_global,
+ * bit_and_elem, bit_op_shorts, sha_init, sha_load, sha_mix and sha_fini, and the four Poseidon2
+ * row kinds. Refused when the program is decoded, naming the row: checked_bytes rows (no C++
+ * witness generator runs them). A run fails with the reference's message where it has one, followed by
+ * " (cycle N)": "Equality check failed: Expecting [..] == [..]", "WOM A overwritten with [..]
+ * from [..]" (a cell rewritten with the same value is legal), "Illegal recursion op", "Unknown
+ * opcode"; where the reference panics, with the library's own: "input exhausted: ...",
+ * "READ_IOP_BODY on an empty IOP body", "READ_IOP_HEADER while the IOP body has K unread
+ * values", "WOM read of address A past the memory's N cells". The library's limit: a WOM address
+ * at or above 16 * 2^po2 cells is refused (the reference grows its memory to any address below
+ * p); the witness generator allows 9 WOM argument rows per cycle, so a program it accepts stays
+ * below.
+ *
+ * r0hip_recursion_preflight: the preflight alone, from the program's words (h_code, n_words,
+ * form and po2 as r0hip_recursion_program_create takes them; no handle, so no device is
+ * needed). Size query: with all four out arrays NULL only the counts are written, and they
+ * depend on the program alone (every write address, READ_IOP_BODY and output position is in the
+ * code). Otherwise all four arrays are given with their capacities (h_wom and h_iops in cells of
+ * 4 words, h_cycles in cycles of 2 words {iop_idx, is_par_safe}, h_output in words) and are
+ * filled as r0hip_recursion_witgen takes them: WOM and IOP values as Montgomery words, the
+ * output (Preflight.output) as plain integers. On a run-time failure h_cycles is complete and
+ * the other arrays hold what the run wrote before it stopped. */
+/* [host-only] */
+const char* r0hip_recursion_preflight(const uint32_t* h_code, size_t n_words, int form, uint32_t po2,
+                                      const uint32_t* h_input, size_t n_input, uint32_t* h_wom, size_t wom_cap,
+                                      size_t* n_wom, uint32_t* h_cycles, size_t cycles_cap, size_t* n_cycles,
+                                      uint32_t* h_iops, size_t iops_cap, size_t* n_iops, uint32_t* h_output,
+                                      size_t output_cap, size_t* n_output);
+/* Makes what every proof from input shares, once per handle: on the host the decoded op table
+ * with each cycle's {iop_idx, is_par_safe}; on the device, in one dedicated allocation, the
+ * witness generator's plan (the exec runs, each cycle's first IOP value, the runs ordered by
+ * bucket; the bucket counts stay on the host). Idempotent and thread-safe; the from-input entry
+ * points call it themselves. r0hip_recursion_program_info and its device_bytes do not change;
+ * r0hip_recursion_program_input_info reports the plan. Freed by r0hip_recursion_program_destroy. */
+/* [drains] */
+const char* r0hip_recursion_program_prepare_input(const r0hip_recursion_program* program);
+typedef struct r0hip_recursion_input_info {
+  uint32_t prepared;           /* 0: not prepared yet, every other field 0 */
+  uint32_t n_runs;             /* exec runs (MachineContext::parStepExec) */
+  uint32_t bucket_runs[9];     /* runs per specialised exec launch */
+  size_t n_wom;                /* WOM cells of a complete run */
+  size_t n_iops;               /* IOP values */
+  size_t n_output;             /* output words */
+  uint64_t n_input;            /* input words the READ_IOP_HEADER ops consume */
+  uint64_t plan_device_bytes;  /* the plan's dedicated allocation */
+  uint64_t plan_host_bytes;    /* op table and cycle table */
+} r0hip_recursion_input_info;
+/* [host-only] */
+const char* r0hip_recursion_program_input_info(const r0hip_recursion_program* program,
+                                               r0hip_recursion_input_info* out);
+/* RecursionProver::prove(program, input) from a handle: the preflight on the calling thread
+ * (written straight into page-locked staging while the group fills run), witness generation
+ * from the handle's plan (no run keys, no run sort, no host synchronisation before the final
+ * error read; only the WOM and the IOP values are copied up), then r0hip_prove_recursion_program's
+ * sequence. Seal and mix are word for word those of r0hip_prove_recursion_program on the
+ * preflight's arrays with the same key and stream_id. h_output (optional, output_cap words)
+ * receives Preflight.output; n_output (optional) its length, written before a too-small buffer
+ * is refused. A preflight failure is returned as the error. */
+/* [drains] */
+const char* r0hip_prove_recursion_program_input(const r0hip_recursion_program* program, const uint32_t* h_input,
+                                                size_t n_input, const uint32_t* h_key, uint64_t stream_id,
+                                                uint32_t* h_seal, size_t seal_cap, size_t* seal_len,
+                                                uint32_t* h_mix_out, uint32_t* h_output, size_t output_cap,
+                                                size_t* n_output);
+/* Host milliseconds of the preflight inside the calling thread's last
+ * r0hip_prove_recursion_program_input (0 before the first): a thread's figure, like
+ * r0hip_last_profile, for benchmarks that report the call less its preflight. */
+/* [host-only] */
+const char* r0hip_recursion_last_preflight_ms(double* out);
 /* Frees the handle and its device memory (after it and r0hip_trim, r0hip_mem_stats' live bytes
  * are what they were before create). While a proof runs from the handle or a worker job that
  * names it has not been handed back, it returns an error and frees nothing. */
@@ -723,6 +796,25 @@ typedef struct r0hip_worker_program_job {
   r0hip_worker_job job;                   /* kind 3; recursion: all but h_ctrl */
   const r0hip_recursion_program* program; /* the resident program */
 } r0hip_worker_program_job;
+/* a job of kind R0HIP_JOB_RECURSION_INPUT: a recursion job from a resident program and the
+ * reference's `input` (r0hip_prove_recursion_program_input with the worker's key and stream_id =
+ * the ticket, so its seal equals the kind-3 seal of the same input's preflight and ticket).
+ * Submitted and handed back by the address of its `job` member, as kind 3 is; of job.recursion
+ * only the allow-list is read. Submit refuses a NULL handle, a suite or po2 that is not the
+ * handle's, po2 above max_po2, and takes a use count that lasts until the job can be handed back.
+ * The preflight runs on the uploader thread while the provers work, into page-locked buffers of
+ * the job's set; its failure lands in this job's error alone. With verify and no allow-list the
+ * seal is checked against the handle's control id. */
+#define R0HIP_JOB_RECURSION_INPUT 4
+typedef struct r0hip_worker_input_job {
+  r0hip_worker_job job;                   /* kind 4 */
+  const r0hip_recursion_program* program; /* the resident program */
+  const uint32_t* h_input;                /* the input words, valid until the job is handed back */
+  size_t n_input;
+  uint32_t* h_output;                     /* out (optional): Preflight.output, output_cap words */
+  size_t output_cap;
+  size_t n_output;                        /* out: the output's length */
+} r0hip_worker_input_job;
 /* [drains] */
 const char* r0hip_worker_create(r0hip_worker** out, uint32_t max_po2, uint32_t in_flight, int verify,
                                 const uint32_t* h_noise_key);

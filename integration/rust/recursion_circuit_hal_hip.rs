@@ -38,6 +38,17 @@ pub struct HipRecursionCircuitHal<HS: HipHash> { _hal: Rc<HipHal<HS>> }
 //     // on the worker: R0HipWorkerProgramJob { job: R0HipWorkerJob { kind: R0HIP_JOB_RECURSION_PROGRAM,
 //     //                 recursion: {..}, .. }, program: h }, submitted as &mut pj.job
 //
+// With the handle, RecursionProver::prove(program, input) (prove/mod.rs:165) needs no Preflight on
+// the Rust side: the library runs it natively and generates the witness from a plan kept in the handle:
+//
+//     r0hip_prove_recursion_program_input(h, input.as_ptr(), input.len(), null(), task_id,
+//         seal, seal_cap, &mut seal_len, mix, output, output_cap, &mut n_output)
+//     // on the worker: R0HipWorkerInputJob { job: R0HipWorkerJob { kind: R0HIP_JOB_RECURSION_INPUT, .. },
+//     //                 program: h, h_input, n_input, h_output, output_cap, n_output: 0 }, as &mut ij.job
+//
+// r0hip_recursion_preflight (host only) gives wom, cycles, iops and output for a cross-check against
+// Preflight::step. Programs with checked_bytes rows are refused and keep the path above.
+//
 // r0hip_recursion_program_info's control_id is Program::compute_control_id (program.rs:74-104) for
 // the HAL's suite. The per-op path below keeps taking `ctrl` as a buffer; r0hip_recursion_program_ctrl
 // gives the handle's control group for it. Drop: r0hip_recursion_program_destroy per handle, after

@@ -92,6 +92,7 @@ pub const R0HIP_JOB_RV32IM_TRACE: u32 = 0;
 pub const R0HIP_JOB_RECURSION: u32 = 1;
 pub const R0HIP_JOB_RV32IM_BACKS: u32 = 2;
 pub const R0HIP_JOB_RECURSION_PROGRAM: u32 = 3;
+pub const R0HIP_JOB_RECURSION_INPUT: u32 = 4;
 
 /// Forms of the code words r0hip_recursion_program_create takes (R0HIP_CODE_*).
 pub const R0HIP_CODE_ENCODED: c_int = 0; // plain u32 words of a .zkr (Elem::from per word)
@@ -176,6 +177,33 @@ pub struct R0HipWorkerJob {
 pub struct R0HipWorkerProgramJob {
     pub job: R0HipWorkerJob,
     pub program: *const R0HipRecursionProgram,
+}
+
+/// A job of kind R0HIP_JOB_RECURSION_INPUT (struct r0hip_worker_input_job): the job, the handle
+/// and the words RecursionProver::prove calls `input`. Submit `&mut ij.job`.
+#[repr(C)]
+pub struct R0HipWorkerInputJob {
+    pub job: R0HipWorkerJob,
+    pub program: *const R0HipRecursionProgram,
+    pub h_input: *const u32,
+    pub n_input: usize,
+    pub h_output: *mut u32,
+    pub output_cap: usize,
+    pub n_output: usize,
+}
+
+/// What r0hip_recursion_program_prepare_input made (struct r0hip_recursion_input_info).
+#[repr(C)]
+pub struct R0HipRecursionInputInfo {
+    pub prepared: u32,
+    pub n_runs: u32,
+    pub bucket_runs: [u32; 9],
+    pub n_wom: usize,
+    pub n_iops: usize,
+    pub n_output: usize,
+    pub n_input: u64,
+    pub plan_device_bytes: u64,
+    pub plan_host_bytes: u64,
 }
 
 #[link(name = "r0hip")]
@@ -544,6 +572,50 @@ unsafe extern "C" {
     ) -> *const c_char;
     /// refused (nothing freed) while a proof or a queued worker job uses the handle
     pub fn r0hip_recursion_program_destroy(program: *mut R0HipRecursionProgram) -> *const c_char;
+    /// The native preflight (Preflight::step, prove/preflight.rs:181-627) of a program's words on
+    /// `input`; all four out arrays null: the size query. Host only.
+    pub fn r0hip_recursion_preflight(
+        h_code: *const u32,
+        n_words: usize,
+        form: c_int,
+        po2: u32,
+        h_input: *const u32,
+        n_input: usize,
+        h_wom: *mut u32,
+        wom_cap: usize,
+        n_wom: *mut usize,
+        h_cycles: *mut u32,
+        cycles_cap: usize,
+        n_cycles: *mut usize,
+        h_iops: *mut u32,
+        iops_cap: usize,
+        n_iops: *mut usize,
+        h_output: *mut u32,
+        output_cap: usize,
+        n_output: *mut usize,
+    ) -> *const c_char;
+    pub fn r0hip_recursion_program_prepare_input(program: *const R0HipRecursionProgram) -> *const c_char;
+    pub fn r0hip_recursion_last_preflight_ms(out: *mut f64) -> *const c_char;
+    pub fn r0hip_recursion_program_input_info(
+        program: *const R0HipRecursionProgram,
+        out: *mut R0HipRecursionInputInfo,
+    ) -> *const c_char;
+    /// RecursionProver::prove(program, input) from a handle: preflight, planned witness generation,
+    /// r0hip_prove_recursion_program's sequence
+    pub fn r0hip_prove_recursion_program_input(
+        program: *const R0HipRecursionProgram,
+        h_input: *const u32,
+        n_input: usize,
+        h_key: *const u32,
+        stream_id: u64,
+        h_seal: *mut u32,
+        seal_cap: usize,
+        seal_len: *mut usize,
+        h_mix_out: *mut u32,
+        h_output: *mut u32,
+        output_cap: usize,
+        n_output: *mut usize,
+    ) -> *const c_char;
     pub fn r0hip_prove_segments(
         circuit: *const c_char,
         suite: c_int,

@@ -14,15 +14,18 @@
 #include <cstdlib>
 #include <algorithm>
 #include <atomic>
+#include <chrono>
 #include <cstring>
 #include <functional>
 #include <memory>
+#include <mutex>
 #include <stdexcept>
 #include <vector>
 
 #include "backs.h"
 #include "circuit.h"
 #include "devmem.h"
+#include "recursion_preflight.h"
 #include "runtime.h"
 #include "rv32im_witgen.h"
 
@@ -471,8 +474,15 @@ struct r0hip_recursion_program {
   uint32_t control_id[8] = {};
   std::vector<uint32_t> top;
   mutable std::atomic<uint64_t> uses{0};  // proofs running and worker jobs queued
+  // r0hip_recursion_program_prepare_input: the op table and fixed tables on the host, the witness
+  // generator's plan on the device; written once under plan_mu, read-only once `planned` is set
+  mutable std::mutex plan_mu;
+  mutable std::atomic<bool> planned{false};
+  mutable r0::rpf::Program ops;
+  mutable r0::RecursionWitgenPlan plan;
   ~r0hip_recursion_program() {
     for (int i = 0; i < 4; i++) dev_free_dedicated(buf[i], bytes[i]);
+    r0::recursion_witgen_plan_free(&plan);
   }
 };
 
@@ -645,10 +655,12 @@ void check_injector(const uint32_t* index, size_t rows, const uint32_t* offsets,
 // RecursionProverImpl::prove from the program and its preflight (circuit/recursion/src/prove/
 // mod.rs:160-230). noise(s, out, count, which) fills `count` words of the ZK noise matrix
 // `which` (0 the data group's, 1 the accum group's) on stream s.
-std::vector<uint32_t> prove_recursion(int suite, uint32_t po2, const uint32_t* d_ctrl, const uint32_t* h_wom,
-                                      size_t n_wom, const uint32_t* h_cycles, size_t n_cycles, const uint32_t* h_iops,
-                                      size_t n_iops, const RecursionNoise& noise_fill, std::vector<uint32_t>* mix,
-                                      const CachedGroup* ctrl_cached) {
+// witgen(s, data, global): the witness generator, called once the data group and the globals
+// are INVALID words
+using RecursionWitgen = std::function<void(hipStream_t s, uint32_t* data, uint32_t* global)>;
+static std::vector<uint32_t> prove_recursion_with(int suite, uint32_t po2, const uint32_t* d_ctrl, size_t n_cycles,
+                                                  const RecursionWitgen& witgen, const RecursionNoise& noise_fill,
+                                                  std::vector<uint32_t>* mix, const CachedGroup* ctrl_cached) {
   const CircuitDef* c = find_circuit("recursion");
   R0_REQUIRE(c && d_ctrl, "r0hip_prove_recursion: null argument");
   R0_REQUIRE(po2 >= 11 && po2 <= 24, "r0hip_prove_recursion: po2 out of range (ZK rows need po2 >= 11)");
@@ -669,7 +681,7 @@ std::vector<uint32_t> prove_recursion(int suite, uint32_t po2, const uint32_t* d
   if (early) code_early = commit_group_side(1, suite, d_ctrl, c->group_size(1), po2);
   HIP_OK(hipMemsetD32Async(data.p, 0xFFFFFFFFu, data.words, s));
   HIP_OK(hipMemsetD32Async(global.p, 0xFFFFFFFFu, global.words, s));
-  recursion_witgen(s, d_ctrl, data.p, global.p, n, h_wom, n_wom, h_cycles, n_cycles, h_iops, n_iops);
+  witgen(s, data.p, global.p);
   // ZK noise in the last ZK_CYCLES data rows (witgen.rs:101-116: eltwise_copy_elem_slice
   // from a data_size x ZK_CYCLES noise matrix), per-cell values of the noise generator
   noise_fill(s, noise.p, data_cols * kZk, 0);
@@ -683,6 +695,19 @@ std::vector<uint32_t> prove_recursion(int suite, uint32_t po2, const uint32_t* d
   const AccumStep acc{accum.p, n_cycles};
   return prove_segment(*c, suite, po2, d_ctrl, data.p, nullptr, global.p, false, 0, mix, nullptr, &acc,
                        early ? &code_early : nullptr, ctrl_cached);
+}
+
+std::vector<uint32_t> prove_recursion(int suite, uint32_t po2, const uint32_t* d_ctrl, const uint32_t* h_wom,
+                                      size_t n_wom, const uint32_t* h_cycles, size_t n_cycles, const uint32_t* h_iops,
+                                      size_t n_iops, const RecursionNoise& noise_fill, std::vector<uint32_t>* mix,
+                                      const CachedGroup* ctrl_cached) {
+  const size_t n = size_t(1) << (po2 <= 24 ? po2 : 0);
+  return prove_recursion_with(
+      suite, po2, d_ctrl, n_cycles,
+      [&](hipStream_t s, uint32_t* data, uint32_t* global) {
+        recursion_witgen(s, d_ctrl, data, global, n, h_wom, n_wom, h_cycles, n_cycles, h_iops, n_iops);
+      },
+      noise_fill, mix, ctrl_cached);
 }
 
 // The keyed noise of r0hip_prove_recursion_keyed: ChaCha20 under `key`, the data matrix with
@@ -724,6 +749,62 @@ std::vector<uint32_t> prove_recursion_program(const r0hip_recursion_program* h, 
   const CachedGroup cg{h->buf[1], h->buf[2], h->buf[3], 23, h->top.data()};
   return prove_recursion(h->suite, h->po2, h->buf[0], h_wom, n_wom, h_cycles, n_cycles, h_iops, n_iops, noise_fill, mix,
                          &cg);
+}
+
+// host milliseconds of the preflight inside this thread's last prove_recursion_program_input
+static thread_local double t_last_preflight_ms = 0;
+double recursion_last_preflight_ms() { return t_last_preflight_ms; }
+
+// r0hip_recursion_program_prepare_input. The control group comes back from the device (create
+// keeps no host copy and stays as cheap as it was), is decoded once, and the witness generator's
+// plan is made from the decoded {iopIdx, isParSafe}. A failure leaves the handle without a plan
+// and the next call tries again.
+RecursionInputCounts recursion_program_prepare_input(const r0hip_recursion_program* h) {
+  if (!h->planned.load(std::memory_order_acquire)) {
+    std::lock_guard<std::mutex> lk(h->plan_mu);
+    if (!h->planned.load(std::memory_order_relaxed)) {
+      const size_t n = size_t(1) << h->po2;
+      std::vector<uint32_t> ctrl(23 * n);
+      stage_reset();
+      download(ctrl.data(), h->buf[0], ctrl.size() * 4);
+      rpf::Program ops = rpf::decode_columns(ctrl.data(), h->code_rows, h->po2);
+      recursion_witgen_plan(stream(), h->buf[0], n, ops.cycles.data(), h->code_rows, &h->plan);
+      h->ops = std::move(ops);
+      h->planned.store(true, std::memory_order_release);
+    }
+  }
+  return RecursionInputCounts{h->ops.n_wom, h->ops.n_iops, h->ops.n_output};
+}
+
+void recursion_program_preflight_into(const r0hip_recursion_program* h, const uint32_t* h_input, size_t n_input,
+                                      uint32_t* wom, uint32_t* iops, uint32_t* output) {
+  rpf::run(h->ops, h_input, n_input, wom, iops, output);
+}
+
+std::vector<uint32_t> prove_recursion_program_input(const r0hip_recursion_program* h, const uint32_t* h_input,
+                                                    size_t n_input, const uint32_t* h_wom, const uint32_t* h_iops,
+                                                    uint32_t* output, const RecursionNoise& noise_fill,
+                                                    std::vector<uint32_t>* mix) {
+  const RecursionInputCounts cnt = recursion_program_prepare_input(h);
+  const CachedGroup cg{h->buf[1], h->buf[2], h->buf[3], 23, h->top.data()};
+  return prove_recursion_with(
+      h->suite, h->po2, h->buf[0], h->code_rows,
+      [&](hipStream_t s, uint32_t* data, uint32_t* global) {
+        const uint32_t *wom = h_wom, *iops = h_iops;
+        if (!wom) {
+          // the preflight writes its upload in place (the group fills queued above run meanwhile)
+          Span sp("preflight");
+          auto* w = static_cast<uint32_t*>(stage_host(cnt.n_wom * 16 + 16));
+          auto* i = static_cast<uint32_t*>(stage_host(cnt.n_iops * 16 + 16));
+          const auto t0 = std::chrono::steady_clock::now();
+          rpf::run(h->ops, h_input, n_input, w, i, output);
+          t_last_preflight_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+          wom = w, iops = i;
+        }
+        recursion_witgen_planned(s, h->buf[0], data, global, size_t(1) << h->po2, h->plan, wom, cnt.n_wom, iops,
+                                 cnt.n_iops, true);
+      },
+      noise_fill, mix, &cg);
 }
 
 void os_random_key(uint32_t key[8]) {
@@ -950,6 +1031,100 @@ const char* r0hip_prove_recursion_program(const r0hip_recursion_program* program
     seal_out(seal, mix, h_seal, seal_cap, seal_len, h_mix_out);
   });
   // wrap has drained this thread's stream (on an error too): nothing of the proof reads the handle
+  if (held) recursion_program_release(program);
+  explicit_bzero(key, sizeof key);
+  return err;
+}
+
+const char* r0hip_recursion_preflight(const uint32_t* h_code, size_t n_words, int form, uint32_t po2,
+                                      const uint32_t* h_input, size_t n_input, uint32_t* h_wom, size_t wom_cap,
+                                      size_t* n_wom, uint32_t* h_cycles, size_t cycles_cap, size_t* n_cycles,
+                                      uint32_t* h_iops, size_t iops_cap, size_t* n_iops, uint32_t* h_output,
+                                      size_t output_cap, size_t* n_output) {
+  return wrap_nosync([&] {
+    const std::string who = "r0hip_recursion_preflight: ";
+    R0_REQUIRE(h_input || !n_input, who + "h_input is NULL with n_input " + std::to_string(n_input));
+    const rpf::Program p = rpf::decode(h_code, n_words, form, po2);
+    if (n_wom) *n_wom = p.n_wom;
+    if (n_cycles) *n_cycles = p.ops.size();
+    if (n_iops) *n_iops = p.n_iops;
+    if (n_output) *n_output = p.n_output;
+    if (!h_wom && !h_cycles && !h_iops && !h_output) return;  // the size query
+    R0_REQUIRE(h_wom && h_cycles && h_iops && h_output, who + "pass every out array, or none for the size query");
+    R0_REQUIRE(wom_cap >= p.n_wom && cycles_cap >= p.ops.size() && iops_cap >= p.n_iops && output_cap >= p.n_output,
+               who + "an out array is too small: the program needs " + std::to_string(p.n_wom) + " WOM cells, " +
+                   std::to_string(p.ops.size()) + " cycles, " + std::to_string(p.n_iops) + " IOP values and " +
+                   std::to_string(p.n_output) + " output words");
+    memcpy(h_cycles, p.cycles.data(), p.cycles.size() * 4);
+    rpf::run(p, h_input, n_input, h_wom, h_iops, h_output);
+  });
+}
+
+const char* r0hip_recursion_program_prepare_input(const r0hip_recursion_program* program) {
+  bool held = false;
+  const char* err = wrap([&] {
+    R0_REQUIRE(program, "r0hip_recursion_program_prepare_input: program is NULL");
+    recursion_program_acquire(program);
+    held = true;
+    recursion_program_prepare_input(program);
+  });
+  if (held) recursion_program_release(program);
+  return err;
+}
+
+const char* r0hip_recursion_program_input_info(const r0hip_recursion_program* program, r0hip_recursion_input_info* out) {
+  return wrap_nosync([&] {
+    R0_REQUIRE(program && out, "r0hip_recursion_program_input_info: null argument");
+    *out = r0hip_recursion_input_info{};
+    if (!program->planned.load(std::memory_order_acquire)) return;
+    const rpf::Program& p = program->ops;
+    out->prepared = 1;
+    out->n_runs = program->plan.nruns;
+    for (int k = 0; k < 9; k++) out->bucket_runs[k] = program->plan.counts[k];
+    out->n_wom = p.n_wom;
+    out->n_iops = p.n_iops;
+    out->n_output = p.n_output;
+    out->n_input = p.n_input;
+    out->plan_device_bytes = program->plan.bytes;
+    out->plan_host_bytes = p.ops.size() * sizeof(rpf::Op) + p.cycles.size() * 4;
+  });
+}
+
+const char* r0hip_recursion_last_preflight_ms(double* out) {
+  return wrap_nosync([&] {
+    R0_REQUIRE(out, "r0hip_recursion_last_preflight_ms: out is NULL");
+    *out = recursion_last_preflight_ms();
+  });
+}
+
+const char* r0hip_prove_recursion_program_input(const r0hip_recursion_program* program, const uint32_t* h_input,
+                                                size_t n_input, const uint32_t* h_key, uint64_t stream_id,
+                                                uint32_t* h_seal, size_t seal_cap, size_t* seal_len,
+                                                uint32_t* h_mix_out, uint32_t* h_output, size_t output_cap,
+                                                size_t* n_output) {
+  uint32_t key[8];
+  bool held = false;
+  const char* err = wrap([&] {
+    const std::string who = "r0hip_prove_recursion_program_input: ";
+    R0_REQUIRE(program, who + "program is NULL");
+    R0_REQUIRE(h_input || !n_input, who + "h_input is NULL with n_input " + std::to_string(n_input));
+    R0_REQUIRE(!seal_cap || h_seal, who + "h_seal is NULL with seal_cap " + std::to_string(seal_cap));
+    R0_REQUIRE(!output_cap || h_output, who + "h_output is NULL with output_cap " + std::to_string(output_cap));
+    recursion_program_acquire(program);
+    held = true;
+    const RecursionInputCounts cnt = recursion_program_prepare_input(program);
+    if (n_output) *n_output = cnt.n_output;
+    R0_REQUIRE(!h_output || cnt.n_output <= output_cap, who + "output buffer too small: the program writes " +
+                                                            std::to_string(cnt.n_output) + " words");
+    std::vector<uint32_t> output(cnt.n_output);
+    if (h_key) memcpy(key, h_key, sizeof key);
+    else os_random_key(key);
+    std::vector<uint32_t> mix;
+    auto seal = prove_recursion_program_input(program, h_input, n_input, nullptr, nullptr, output.data(),
+                                              keyed_noise(key, stream_id), &mix);
+    seal_out(seal, mix, h_seal, seal_cap, seal_len, h_mix_out);
+    if (h_output && cnt.n_output) memcpy(h_output, output.data(), cnt.n_output * 4);
+  });
   if (held) recursion_program_release(program);
   explicit_bzero(key, sizeof key);
   return err;

@@ -402,8 +402,32 @@ const char* prove_trace_jobs(int suite, uint32_t po2, r0hip_trace_job* jobs, siz
 // kind R0HIP_JOB_RECURSION_PROGRAM stages nothing and grows nothing: its control group and the
 // group's commitment live in the caller's handle, on which the job holds a use count from
 // submit to finish().
+// page-locked host words that grow (a kind-4 job's preflight is written here by the uploader and
+// copied to the device by the set's prover without staging)
+struct PinnedWords {
+  uint32_t* p = nullptr;
+  size_t words = 0;
+  PinnedWords() = default;
+  PinnedWords(const PinnedWords&) = delete;
+  PinnedWords& operator=(const PinnedWords&) = delete;
+  PinnedWords(PinnedWords&& o) noexcept : p(o.p), words(o.words) { o.p = nullptr, o.words = 0; }
+  ~PinnedWords() {
+    if (p) (void)hipHostFree(p);
+  }
+  void reserve(size_t n) {
+    if (n <= words) return;
+    if (p) (void)hipHostFree(p);
+    p = nullptr, words = 0;
+    void* q = nullptr;
+    HIP_OK(hipHostMalloc(&q, n * 4, hipHostMallocDefault));
+    p = static_cast<uint32_t*>(q), words = n;
+  }
+};
+
 struct WorkerSet : TraceSet {
   DevBuf ctrl;  // recursion jobs: the control group (allocated at the set's first one)
+  PinnedWords pf_wom, pf_iops;  // kind-4 jobs: the preflight's WOM and IOP values
+  std::vector<uint32_t> pf_out;
   r0hip_worker_job* wjob = nullptr;
   size_t cap_inj = 0, cap_txn = 0, cap_big = 0;  // entries, records, bytes
   // kind-2 jobs: the Back records and their payload words (allocated at the set's first one),
@@ -414,9 +438,15 @@ struct WorkerSet : TraceSet {
   std::vector<r0hip_bigint_back> backs_bigint;
 };
 
-// a job of kind R0HIP_JOB_RECURSION_PROGRAM is the first member of an r0hip_worker_program_job
+// a job of kind R0HIP_JOB_RECURSION_PROGRAM is the first member of an r0hip_worker_program_job,
+// one of kind R0HIP_JOB_RECURSION_INPUT of an r0hip_worker_input_job: the handle follows the job
+static_assert(offsetof(r0hip_worker_input_job, program) == offsetof(r0hip_worker_program_job, program),
+              "the handle sits at one offset in both job structs");
 inline const r0hip_recursion_program* job_program(const r0hip_worker_job* j) {
   return reinterpret_cast<const r0hip_worker_program_job*>(j)->program;
+}
+inline bool job_holds_program(const r0hip_worker_job* j) {
+  return j->kind == R0HIP_JOB_RECURSION_PROGRAM || j->kind == R0HIP_JOB_RECURSION_INPUT;
 }
 
 struct WorkerImpl {
@@ -442,7 +472,7 @@ struct WorkerImpl {
   void finish(r0hip_worker_job* j) {
     // the job's proof has drained (or never ran): its hold on a resident program ends here,
     // before r0hip_worker_wait can hand the job back
-    if (j->kind == R0HIP_JOB_RECURSION_PROGRAM) recursion_program_release(job_program(j));
+    if (job_holds_program(j)) recursion_program_release(job_program(j));
     {
       std::lock_guard<std::mutex> lk(mu);
       finished.push_back(j);
@@ -464,7 +494,7 @@ struct WorkerImpl {
       if (b.ctrl.words < 23 * n) b.ctrl = DevBuf(23 * n);
       return;
     }
-    if (j.kind == R0HIP_JOB_RECURSION_PROGRAM) return;  // the control group lives in the handle
+    if (job_holds_program(&j)) return;  // the control group lives in the handle
     const r0hip_trace_input& t = j.trace;
     if (j.kind == R0HIP_JOB_RV32IM_BACKS) {  // checked at submit: at most n records, n_words below 2^32
       if (j.backs->n > b.cap_recs) {
@@ -541,6 +571,23 @@ struct WorkerImpl {
             HIP_OK(hipEventRecord(b.ev, stream()));
           } else if (j->kind == R0HIP_JOB_RECURSION_PROGRAM) {
             // nothing to stage: the prover reads the handle and the job's host arrays
+          } else if (j->kind == R0HIP_JOB_RECURSION_INPUT) {
+            // the preflight, here, while the provers work: into the set's page-locked buffers,
+            // which its prover copies up itself. Nothing stays queued on this thread's stream: the
+            // first job of a handle makes its plan here (a read-back, the run keys and their sort),
+            // and recursion_program_prepare_input drains before it returns
+            auto* ij = reinterpret_cast<r0hip_worker_input_job*>(j);
+            const RecursionInputCounts cnt = recursion_program_prepare_input(job_program(j));
+            ij->n_output = cnt.n_output;
+            R0_REQUIRE(!ij->h_output || cnt.n_output <= ij->output_cap,
+                       "recursion input job: output buffer too small: the program writes " +
+                           std::to_string(cnt.n_output) + " words");
+            b.pf_wom.reserve(cnt.n_wom * 4 + 4);
+            b.pf_iops.reserve(cnt.n_iops * 4 + 4);
+            b.pf_out.resize(cnt.n_output);
+            recursion_program_preflight_into(job_program(j), ij->h_input, ij->n_input, b.pf_wom.p, b.pf_iops.p,
+                                             b.pf_out.data());
+            if (ij->h_output && cnt.n_output) memcpy(ij->h_output, b.pf_out.data(), cnt.n_output * 4);
           } else if (j->kind == R0HIP_JOB_RV32IM_BACKS) {
             // the records were checked at submit; no index, offsets or values are staged
             const r0hip_raw_preflight_trace& pf = j->trace.preflight;
@@ -603,6 +650,14 @@ struct WorkerImpl {
           const r0hip_recursion_input& in = j->recursion;
           seal = prove_recursion_program(job_program(j), in.h_wom, in.n_wom, in.h_cycles, in.n_cycles, in.h_iops,
                                          in.n_iops, keyed_noise(key, j->ticket), &mix);
+        } else if (j->kind == R0HIP_JOB_RECURSION_INPUT) {
+          b.wait_landed();  // the uploader has run the preflight into the set's buffers
+          {
+            std::lock_guard<std::mutex> lk(b.mu);
+            if (j->error) throw std::runtime_error(j->error);
+          }
+          seal = prove_recursion_program_input(job_program(j), nullptr, 0, b.pf_wom.p, b.pf_iops.p, nullptr,
+                                               keyed_noise(key, j->ticket), &mix);
         } else if (j->kind == R0HIP_JOB_RV32IM_BACKS) {
           // the set's counts and BigInt records were written by the uploader before the hand-over
           // (grow); the record and word counts are the caller's, checked at submit
@@ -646,12 +701,12 @@ struct WorkerImpl {
       }
       r0hip_worker_job* j = item.first;
       if (!j) return;
-      const bool rec = j->kind == R0HIP_JOB_RECURSION || j->kind == R0HIP_JOB_RECURSION_PROGRAM;
+      const bool rec = j->kind == R0HIP_JOB_RECURSION || job_holds_program(j);
       const auto t0 = std::chrono::steady_clock::now();
       uint32_t got = 0;
       const uint32_t* roots = rec ? j->recursion.h_code_roots : nullptr;
       size_t n_roots = rec ? j->recursion.n_code_roots : 0;
-      if (j->kind == R0HIP_JOB_RECURSION_PROGRAM && n_roots == 0) {
+      if (job_holds_program(j) && n_roots == 0) {
         // no allow-list given: the seal must carry the handle's own control id
         roots = recursion_program_shape(job_program(j)).control_id;
         n_roots = 1;
@@ -968,7 +1023,8 @@ extern "C" const char* r0hip_worker_submit(r0hip_worker* w, r0hip_worker_job* jo
     R0_REQUIRE(w && job, "r0hip_worker_submit: null argument");
     WorkerImpl& m = w->impl;
     R0_REQUIRE(job->kind == R0HIP_JOB_RV32IM_TRACE || job->kind == R0HIP_JOB_RECURSION ||
-                   job->kind == R0HIP_JOB_RV32IM_BACKS || job->kind == R0HIP_JOB_RECURSION_PROGRAM,
+                   job->kind == R0HIP_JOB_RV32IM_BACKS || job->kind == R0HIP_JOB_RECURSION_PROGRAM ||
+                   job->kind == R0HIP_JOB_RECURSION_INPUT,
                "r0hip_worker_submit: unknown job kind");
     BacksInfo info;
     R0_REQUIRE(job->suite >= 0 && job->suite <= 2, "r0hip_worker_submit: unknown hash suite");
@@ -996,6 +1052,17 @@ extern "C" const char* r0hip_worker_submit(r0hip_worker* w, r0hip_worker_job* jo
       R0_REQUIRE((in.h_wom || !in.n_wom) && (in.h_cycles || !in.n_cycles) && (in.h_iops || !in.n_iops) &&
                      (in.h_code_roots || !in.n_code_roots),
                  "r0hip_worker_submit: recursion program job: null argument");
+    } else if (job->kind == R0HIP_JOB_RECURSION_INPUT) {
+      const auto* ij = reinterpret_cast<const r0hip_worker_input_job*>(job);
+      R0_REQUIRE(ij->program, "r0hip_worker_submit: recursion input job: program is NULL");
+      const RecursionProgramShape sh = recursion_program_shape(ij->program);
+      R0_REQUIRE(sh.suite == job->suite, "r0hip_worker_submit: the program's suite " + std::to_string(sh.suite) +
+                                             " is not the job's suite " + std::to_string(job->suite));
+      R0_REQUIRE(sh.po2 == job->po2, "r0hip_worker_submit: the program's po2 " + std::to_string(sh.po2) +
+                                         " is not the job's po2 " + std::to_string(job->po2));
+      R0_REQUIRE((ij->h_input || !ij->n_input) && (ij->h_output || !ij->output_cap) &&
+                     (job->recursion.h_code_roots || !job->recursion.n_code_roots),
+                 "r0hip_worker_submit: recursion input job: null argument");
     } else if (job->kind == R0HIP_JOB_RV32IM_BACKS) {
       R0_REQUIRE(job->po2 >= 2, "r0hip_worker_submit: po2 out of range");
       check_backs_trace(job->trace, "r0hip_worker_submit");
@@ -1018,7 +1085,7 @@ extern "C" const char* r0hip_worker_submit(r0hip_worker* w, r0hip_worker_job* jo
       std::lock_guard<std::mutex> lk(m.mu);
       R0_REQUIRE(!m.stopping, "r0hip_worker_submit: the worker is shutting down");
       // the last thing that can refuse: a queued job holds the program until finish()
-      if (job->kind == R0HIP_JOB_RECURSION_PROGRAM) recursion_program_acquire(job_program(job));
+      if (job_holds_program(job)) recursion_program_acquire(job_program(job));
       job->ticket = m.next_ticket++;
       m.outstanding++;
       m.fifo.emplace_back(job, info);

@@ -305,4 +305,147 @@ void recursion_witgen(hipStream_t s, const uint32_t* ctrl, uint32_t* data, uint3
   R0_REQUIRE(h_err[0] == 0, "recursion witgen: " + witgen_error(h_err[0], h_err[1]));
 }
 
+// ---- the same from a plan (r0hip_recursion_program_prepare_input) ----
+// isParSafe and iopIdx are functions of the program's rows, so the runs, their buckets and the
+// bucket order are too: recursion_witgen's run_key_kernel and run sort run once here, and their
+// results stay on the device. Layout of the one allocation, each part 256-byte aligned:
+// run_start[nruns + 1], iop_idx[ncycles], order[nruns].
+void recursion_witgen_plan(hipStream_t s, const uint32_t* ctrl, size_t total_cycles, const uint32_t* h_cycles,
+                           size_t ncycles, RecursionWitgenPlan* plan) {
+  R0_REQUIRE(plan && !plan->buf, "recursion_witgen_plan: the plan is already built");
+  R0_REQUIRE(total_cycles >= 4 && (total_cycles & (total_cycles - 1)) == 0 && total_cycles <= (size_t(1) << 24),
+             "recursion_witgen_plan: total_cycles must be a power of two in [4, 2^24]");
+  R0_REQUIRE(ctrl && h_cycles && ncycles != 0 && ncycles <= total_cycles, "recursion_witgen_plan: bad cycle count");
+  R0_REQUIRE(ncycles * kMaxWomRows < (size_t(1) << 31), "recursion_witgen_plan: too many cycles");
+  std::vector<uint32_t> run_start, iop_idx(ncycles);
+  for (size_t c = 0; c < ncycles; c++) {
+    iop_idx[c] = h_cycles[2 * c];
+    if (c == 0 || h_cycles[2 * c + 1] != 0) run_start.push_back(uint32_t(c));
+  }
+  const uint32_t nruns = uint32_t(run_start.size());
+  run_start.push_back(uint32_t(ncycles));
+  auto pad = [](size_t words) { return (words + 63) & ~size_t(63); };
+  const size_t o_idx = pad(size_t(nruns) + 1), o_order = o_idx + pad(ncycles), words = o_order + pad(nruns);
+  uint32_t* buf = static_cast<uint32_t*>(dev_alloc_dedicated(words * 4));
+  try {
+    upload_async(buf, run_start.data(), run_start.size() * 4);
+    upload_async(buf + o_idx, iop_idx.data(), ncycles * 4);
+    DevBuf key(nruns), idx(nruns), key2(nruns), counts(kBuckets);
+    HIP_OK(hipMemsetD32Async(counts.p, 0, kBuckets, s));
+    hipLaunchKernelGGL(run_key_kernel, dim3((nruns + kT - 1) / kT), dim3(kT), 0, s, ctrl, uint32_t(total_cycles), buf,
+                       nruns, key.p, idx.p, counts.p);
+    HIP_OK(hipGetLastError());
+    size_t sort_bytes = 0;
+    HIP_OK(hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, key.p, key2.p, idx.p, buf + o_order, int(nruns), 0,
+                                              4, s));
+    void* sort_temp = scratch(sort_bytes + 256, kSlotWitgenRunTemp);
+    HIP_OK(hipcub::DeviceRadixSort::SortPairs(sort_temp, sort_bytes, key.p, key2.p, idx.p, buf + o_order, int(nruns), 0,
+                                              4, s));
+    HIP_OK(hipMemcpyAsync(plan->counts, counts.p, sizeof(plan->counts), hipMemcpyDeviceToHost, s));
+    HIP_OK(hipStreamSynchronize(s));
+    uint32_t total = 0;
+    for (uint32_t k = 0; k < kBuckets; k++) total += plan->counts[k];
+    R0_REQUIRE(total == nruns, "recursion_witgen_plan: run buckets do not cover the runs");
+  } catch (...) {
+    drain_after_error();
+    dev_free_dedicated(buf, words * 4);
+    throw;
+  }
+  plan->buf = buf;
+  plan->bytes = words * 4;
+  plan->run_start = buf;
+  plan->iop_idx = buf + o_idx;
+  plan->order = buf + o_order;
+  plan->nruns = nruns;
+  plan->ncycles = ncycles;
+}
+
+void recursion_witgen_plan_free(RecursionWitgenPlan* plan) noexcept {
+  if (plan->buf) dev_free_dedicated(plan->buf, plan->bytes);
+  *plan = RecursionWitgenPlan{};
+}
+
+void recursion_witgen_planned(hipStream_t s, const uint32_t* ctrl, uint32_t* data, uint32_t* global,
+                              size_t total_cycles, const RecursionWitgenPlan& plan, const uint32_t* h_wom,
+                              size_t n_wom, const uint32_t* h_iops, size_t n_iops, bool pinned) {
+  const size_t ncycles = plan.ncycles;
+  R0_REQUIRE(plan.buf && ncycles != 0 && ncycles <= total_cycles, "recursion_witgen_planned: no plan for this group");
+  R0_REQUIRE((n_wom == 0 || h_wom) && (n_iops == 0 || h_iops),
+             "recursion_witgen_planned: null trace array with a nonzero count");
+  const size_t nrows = ncycles * kMaxWomRows;  // below 2^31: checked when the plan was made
+  uint32_t* d_wom = static_cast<uint32_t*>(scratch(n_wom * 16 + 16, kSlotWitgenWom));
+  uint32_t* d_iops = static_cast<uint32_t*>(scratch(n_iops * 16 + 16, kSlotWitgenIops));
+  if (pinned) {
+    if (n_wom) HIP_OK(hipMemcpyAsync(d_wom, h_wom, n_wom * 16, hipMemcpyHostToDevice, s));
+    if (n_iops) HIP_OK(hipMemcpyAsync(d_iops, h_iops, n_iops * 16, hipMemcpyHostToDevice, s));
+  } else {
+    upload_async(d_wom, h_wom, n_wom * 16);
+    upload_async(d_iops, h_iops, n_iops * 16);
+  }
+  DevBuf rows(nrows * kRowWords), sorted(nrows * kRowWords), count(ncycles), index(ncycles), err(2);
+  DevBuf perm_a(nrows), perm_b(nrows), key_a(nrows), key_b(nrows);
+  HIP_OK(hipMemsetD32Async(rows.p, rwg::kInvalidWord, nrows * kRowWords, s));
+  HIP_OK(hipMemsetD32Async(count.p, 0, ncycles, s));
+  HIP_OK(hipMemsetD32Async(err.p, 0, 2, s));
+
+  rwg::WitgenArgs A{};
+  A.ctrl = ctrl;
+  A.global = global;
+  A.data = data;
+  A.steps = uint32_t(total_cycles);
+  A.ncycles = uint32_t(ncycles);
+  A.run_start = plan.run_start;
+  A.nruns = plan.nruns;
+  A.wom = d_wom;
+  A.n_wom = uint32_t(n_wom);
+  A.iops = d_iops;
+  A.n_iops = uint32_t(n_iops);
+  A.iop_idx = plan.iop_idx;
+  A.rows = rows.p;
+  A.wom_count = count.p;
+  A.wom_index = index.p;
+  A.sorted = sorted.p;
+  A.err = err.p;
+  {
+    KScope ks("recursion_witgen_exec", double(ncycles) * 4 * (23 + 2 * 128));
+    uint32_t off = 0;
+    for (int k = 0; k < int(kBuckets); k++) {
+      recursion_witgen_exec(s, A, k, plan.order + off, plan.counts[k]);
+      off += plan.counts[k];
+    }
+  }
+  {
+    KScope ks("recursion_witgen_sort", double(nrows) * 4 * (kRowWords * 2 + 5 * 6));
+    const uint32_t n = uint32_t(nrows), g = (n + kT - 1) / kT;
+    hipLaunchKernelGGL(iota_kernel, dim3(g), dim3(kT), 0, s, perm_a.p, n);
+    size_t temp_bytes = 0;
+    HIP_OK(hipcub::DeviceRadixSort::SortPairs(nullptr, temp_bytes, key_a.p, key_b.p, perm_a.p, perm_b.p, int(n), 0,
+                                              32, s));
+    size_t scan_bytes = 0;
+    HIP_OK(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, count.p, index.p, int(ncycles), s));
+    void* temp = scratch(std::max(temp_bytes, scan_bytes) + 256, kSlotWitgenTemp);
+    uint32_t* perm = perm_a.p;
+    uint32_t* perm_out = perm_b.p;
+    for (uint32_t pass = 0; pass < 5; pass++) {
+      hipLaunchKernelGGL(row_key_kernel, dim3(g), dim3(kT), 0, s, rows.p, perm, key_a.p, n, pass);
+      HIP_OK(hipcub::DeviceRadixSort::SortPairs(temp, temp_bytes, key_a.p, key_b.p, perm, perm_out, int(n), 0, 32, s));
+      std::swap(perm, perm_out);
+    }
+    hipLaunchKernelGGL(gather_rows_kernel, dim3(g), dim3(kT), 0, s, rows.p, perm, sorted.p, n);
+    HIP_OK(hipcub::DeviceScan::ExclusiveSum(temp, scan_bytes, count.p, index.p, int(ncycles), s));
+    if (ncycles > 1)
+      hipLaunchKernelGGL(inject_backs_kernel, dim3(uint32_t((ncycles - 1 + kT - 1) / kT)), dim3(kT), 0, s, data,
+                         uint32_t(total_cycles), sorted.p, index.p, uint32_t(ncycles));
+    HIP_OK(hipGetLastError());
+  }
+  {
+    KScope ks("recursion_witgen_verify", double(ncycles) * 4 * (23 + 2 * 128));
+    recursion_witgen_verify(s, A);
+  }
+  uint32_t h_err[2] = {0, 0};
+  HIP_OK(hipMemcpyAsync(h_err, err.p, 8, hipMemcpyDeviceToHost, s));
+  HIP_OK(hipStreamSynchronize(s));
+  R0_REQUIRE(h_err[0] == 0, "recursion witgen: " + witgen_error(h_err[0], h_err[1]));
+}
+
 }  // namespace r0

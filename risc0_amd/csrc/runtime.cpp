@@ -421,6 +421,11 @@ uint8_t* stage_take(size_t bytes) {
 }
 }  // namespace
 
+void* stage_host(size_t bytes) {
+  ensure_init();
+  return stage_take(bytes);
+}
+
 void upload_async(void* d_dst, const void* h_src, size_t bytes) {
   if (!bytes) return;
   ensure_init();

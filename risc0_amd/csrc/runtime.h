@@ -208,6 +208,9 @@ void join(int k);
 // through upload_async.
 void upload_async(void* d_dst, const void* h_src, size_t bytes);
 void stage_reset();
+// `bytes` of the arena for a producer that writes its upload in place: page-locked, 256-byte
+// aligned, the calling thread's until its next stage_reset; copy from it on the thread's stream.
+void* stage_host(size_t bytes);
 // Device-to-host copy in stream order, complete on return (this thread's stream is drained):
 // small copies into pageable memory bounce through the page-locked arena.
 void download(void* h_dst, const void* d_src, size_t bytes);
@@ -341,6 +344,43 @@ std::vector<uint32_t> prove_recursion_program(const r0hip_recursion_program* h, 
                                               const uint32_t* h_cycles, size_t n_cycles, const uint32_t* h_iops,
                                               size_t n_iops, const RecursionNoise& noise_fill,
                                               std::vector<uint32_t>* mix);
+// What recursion witness generation derives from the program alone (recursion_witgen.hip), kept
+// on the device in one dedicated allocation: the exec runs, each cycle's first IOP value, the
+// runs ordered by bucket, and on the host the runs per bucket.
+struct RecursionWitgenPlan {
+  uint32_t* buf = nullptr;
+  size_t bytes = 0;
+  const uint32_t *run_start = nullptr, *iop_idx = nullptr, *order = nullptr;
+  uint32_t nruns = 0;
+  size_t ncycles = 0;
+  uint32_t counts[9] = {};
+};
+// h_cycles: {iop_idx, is_par_safe} per cycle. Runs today's run keys and their sort once on s and
+// returns with s drained; recursion_witgen_plan_free gives the allocation back.
+void recursion_witgen_plan(hipStream_t s, const uint32_t* ctrl, size_t total_cycles, const uint32_t* h_cycles,
+                           size_t ncycles, RecursionWitgenPlan* plan);
+void recursion_witgen_plan_free(RecursionWitgenPlan* plan) noexcept;
+// recursion_witgen with the runs, their order and the bucket counts read from the plan: no run
+// keys, no run sort and no host synchronisation before the final error read. pinned: h_wom and
+// h_iops are page-locked and stay valid until s has drained (copied without staging).
+void recursion_witgen_planned(hipStream_t s, const uint32_t* ctrl, uint32_t* data, uint32_t* global,
+                              size_t total_cycles, const RecursionWitgenPlan& plan, const uint32_t* h_wom,
+                              size_t n_wom, const uint32_t* h_iops, size_t n_iops, bool pinned);
+// Proofs from a handle and the reference's `input` (api.cpp). prepare: the handle's op table and
+// device plan, made once (thread-safe). preflight_into runs the handle's preflight; wom and iops
+// may be page-locked. prove_recursion_program_input: preflight (into the thread's staging arena
+// when h_wom is NULL, else the given page-locked arrays are taken as a finished preflight),
+// planned witness generation, then prove_recursion_program's sequence.
+struct RecursionInputCounts {
+  size_t n_wom, n_iops, n_output;
+};
+RecursionInputCounts recursion_program_prepare_input(const r0hip_recursion_program* h);
+void recursion_program_preflight_into(const r0hip_recursion_program* h, const uint32_t* h_input, size_t n_input,
+                                      uint32_t* wom, uint32_t* iops, uint32_t* output);
+std::vector<uint32_t> prove_recursion_program_input(const r0hip_recursion_program* h, const uint32_t* h_input,
+                                                    size_t n_input, const uint32_t* h_wom, const uint32_t* h_iops,
+                                                    uint32_t* output, const RecursionNoise& noise_fill,
+                                                    std::vector<uint32_t>* mix);
 // Program.code (rows x 23 words, row-major, on the device) into the control group: 23 columns
 // of 2^po2 words, rows from n_words / 23 on zero, every word of the group written by this launch.
 // form 0: each word x becomes Elem::from(x) (the Montgomery word of x mod p); form 1: copied.

@@ -120,6 +120,13 @@ def _declare(L):
         "r0hip_prove_recursion_program": [vp, u32p, sz, u32p, sz, u32p, sz, u32p, C.c_uint64, u32p, sz, C.POINTER(sz),
                                           u32p],
         "r0hip_recursion_program_destroy": [vp],
+        "r0hip_recursion_preflight": [u32p, sz, C.c_int, C.c_uint32, u32p, sz, u32p, sz, C.POINTER(sz), u32p, sz,
+                                      C.POINTER(sz), u32p, sz, C.POINTER(sz), u32p, sz, C.POINTER(sz)],
+        "r0hip_recursion_program_prepare_input": [vp],
+        "r0hip_recursion_last_preflight_ms": [C.POINTER(C.c_double)],
+        "r0hip_recursion_program_input_info": [vp, vp],
+        "r0hip_prove_recursion_program_input": [vp, u32p, sz, u32p, C.c_uint64, u32p, sz, C.POINTER(sz), u32p, u32p,
+                                                sz, C.POINTER(sz)],
         "r0hip_worker_create": [C.POINTER(vp), C.c_uint32, C.c_uint32, C.c_int, u32p],
         "r0hip_worker_submit": [vp, vp],
         "r0hip_worker_wait": [vp, C.POINTER(vp), C.c_int64],
@@ -606,6 +613,40 @@ def prove_recursion_keyed(hal, po2, ctrl, wom, cycles, iops, key, stream_id, sea
 CODE_ENCODED, CODE_MONTGOMERY = 0, 1
 
 
+class RecursionInputInfo(C.Structure):
+    """struct r0hip_recursion_input_info (include/r0hip.h)"""
+    _fields_ = [("prepared", C.c_uint32), ("n_runs", C.c_uint32), ("bucket_runs", C.c_uint32 * 9),
+                ("n_wom", C.c_size_t), ("n_iops", C.c_size_t), ("n_output", C.c_size_t), ("n_input", C.c_uint64),
+                ("plan_device_bytes", C.c_uint64), ("plan_host_bytes", C.c_uint64)]
+
+
+def recursion_last_preflight_ms():
+    """host milliseconds of the preflight inside this thread's last RecursionProgram.prove_input"""
+    ms = C.c_double(0)
+    check(lib().r0hip_recursion_last_preflight_ms(C.byref(ms)))
+    return ms.value
+
+
+def recursion_preflight(code, po2, inp=(), form=0):
+    """r0hip_recursion_preflight: the native preflight of a program's words (row-major, 23 per
+    row) on `inp`, host only. Returns (wom (k, 4), cycles (rows, 2), iops (m, 4), output), the
+    WOM and IOP values as Montgomery words; raises R0HipError with the preflight's message."""
+    c = np.ascontiguousarray(code, dtype=np.uint32).reshape(-1)
+    x = np.ascontiguousarray(inp, dtype=np.uint32).reshape(-1)
+    n = [C.c_size_t(0) for _ in range(4)]
+    xp = x.ctypes.data_as(u32p) if x.size else None
+    check(lib().r0hip_recursion_preflight(c.ctypes.data_as(u32p), c.size, form, po2, xp, x.size, None, 0,
+                                          C.byref(n[0]), None, 0, C.byref(n[1]), None, 0, C.byref(n[2]), None, 0,
+                                          C.byref(n[3])))
+    # a word past each count, so that no array is empty (an empty array has no address to give)
+    wom, cyc, iops, out = (np.zeros(k.value * w + 1, dtype=np.uint32) for k, w in zip(n, (4, 2, 4, 1)))
+    check(lib().r0hip_recursion_preflight(c.ctypes.data_as(u32p), c.size, form, po2, xp, x.size,
+                                          wom.ctypes.data_as(u32p), n[0].value, None, cyc.ctypes.data_as(u32p),
+                                          n[1].value, None, iops.ctypes.data_as(u32p), n[2].value, None,
+                                          out.ctypes.data_as(u32p), n[3].value, None))
+    return wom[:-1].reshape(-1, 4), cyc[:-1].reshape(-1, 2), iops[:-1].reshape(-1, 4), out[:-1]
+
+
 class RecursionProgram:
     """A recursion program resident on the device (r0hip_recursion_program_*): the control group
     and its commitment, made once from the program's rows and reused by every proof.
@@ -632,6 +673,45 @@ class RecursionProgram:
         check(lib().r0hip_recursion_program_create(C.byref(h), suite, po2, c.ctypes.data_as(u32p),
                                                    c.size if n_words is None else n_words, form))
         return cls(h, suite)
+
+    def preflight(self, inp=()):
+        """the native preflight of this program on `inp` (recursion_preflight), from the control
+        group read back from the device (the handle keeps no host copy of the code)"""
+        _suite, po2, rows, _cid, _dev = self.info()
+        code = np.ascontiguousarray(self.ctrl().reshape(23, 1 << po2)[:, :rows].T)
+        return recursion_preflight(code, po2, inp, CODE_MONTGOMERY)
+
+    def prepare_input(self):
+        """r0hip_recursion_program_prepare_input: the op table and the witness generator's plan,
+        made once (prove_input and Worker.submit_recursion_input call it themselves)"""
+        check(lib().r0hip_recursion_program_prepare_input(self._handle()))
+
+    def input_info(self):
+        """r0hip_recursion_program_input_info as a RecursionInputInfo"""
+        info = RecursionInputInfo()
+        check(lib().r0hip_recursion_program_input_info(self._handle(), C.addressof(info)))
+        return info
+
+    def prove_input(self, inp, key, stream_id, seal_cap=1 << 24):
+        """r0hip_prove_recursion_program_input: RecursionProver::prove(program, input). Returns
+        (seal, mix, output): the seal and mix of prove() on the preflight's arrays with the same
+        key and stream_id, and Preflight.output."""
+        x = np.ascontiguousarray(inp, dtype=np.uint32).reshape(-1)
+        k, kp = _key_words(key)
+        seal = np.zeros(seal_cap, dtype=np.uint32)
+        n, n_out = C.c_size_t(0), C.c_size_t(0)
+        mix = np.zeros(20, dtype=np.uint32)
+        h = self._handle()
+        info = self.input_info()
+        if not info.prepared:  # once: the call below would do it too, but n_output sizes the buffer
+            self.prepare_input()
+            info = self.input_info()
+        out = np.zeros(info.n_output + 1, dtype=np.uint32)
+        check(lib().r0hip_prove_recursion_program_input(h, x.ctypes.data_as(u32p) if x.size else None, x.size, kp,
+                                                        stream_id, seal.ctypes.data_as(u32p), seal_cap, C.byref(n),
+                                                        mix.ctypes.data_as(u32p), out.ctypes.data_as(u32p),
+                                                        out.size - 1, C.byref(n_out)))
+        return seal[: n.value].copy(), mix, out[: n_out.value].copy()
 
     def __enter__(self):
         return self
@@ -992,7 +1072,14 @@ class WorkerProgramJobStruct(C.Structure):
     _fields_ = [("job", WorkerJobStruct), ("program", C.c_void_p)]
 
 
-JOB_RV32IM_TRACE, JOB_RECURSION, JOB_RV32IM_BACKS, JOB_RECURSION_PROGRAM = 0, 1, 2, 3
+class WorkerInputJobStruct(C.Structure):
+    """struct r0hip_worker_input_job (include/r0hip.h): a kind-4 job, the job struct followed by
+    the resident program's handle and the input words; its `job` member is what submit takes"""
+    _fields_ = [("job", WorkerJobStruct), ("program", C.c_void_p), ("h_input", C.c_void_p), ("n_input", C.c_size_t),
+                ("h_output", C.c_void_p), ("output_cap", C.c_size_t), ("n_output", C.c_size_t)]
+
+
+JOB_RV32IM_TRACE, JOB_RECURSION, JOB_RV32IM_BACKS, JOB_RECURSION_PROGRAM, JOB_RECURSION_INPUT = 0, 1, 2, 3, 4
 
 
 class BacksJob:
@@ -1034,6 +1121,7 @@ class Worker:
     def __init__(self, hal, max_po2, in_flight=2, verify=True, noise_key=None, seal_cap=1 << 22):
         self.hal, self.verify, self.seal_cap = hal, bool(verify), seal_cap
         self._pending = {}  # address of the job struct -> (struct, seal, mix, inputs)
+        self.outputs = {}  # ticket of a returned kind-4 job -> Preflight.output, until output() reads it
         k, kp = _key_words(noise_key)
         h = C.c_void_p()
         check(lib().r0hip_worker_create(C.byref(h), max_po2, in_flight, int(self.verify), kp))
@@ -1063,6 +1151,7 @@ class Worker:
             if job.error:
                 libc_free(job.error)
         self._pending.clear()
+        self.outputs.clear()
         check(err)
 
     def _handle(self):
@@ -1142,6 +1231,35 @@ class Worker:
                                        roots.ctypes.data if roots.size else None, roots.size // 8)
         return self._submit(job, 20, (pj, program, w, c, i, roots))
 
+    def submit_recursion_input(self, program, inp, code_roots=None, po2=None, suite=None):
+        """queue one recursion proof from a RecursionProgram and the reference's `input` (kind
+        R0HIP_JOB_RECURSION_INPUT): the preflight runs on the worker's uploader thread. Returns
+        its ticket; output(ticket) gives Preflight.output once wait() has returned the job."""
+        x = np.ascontiguousarray(inp, dtype=np.uint32).reshape(-1)
+        roots = np.ascontiguousarray(np.zeros(0, np.uint32) if code_roots is None else code_roots,
+                                     dtype=np.uint32).reshape(-1)
+        if roots.size % 8:
+            raise R0HipError("code_roots holds 8 words per root")
+        p_suite, p_po2 = program.info()[:2]
+        if not program.input_info().prepared:
+            program.prepare_input()
+        out = np.zeros(program.input_info().n_output + 1, dtype=np.uint32)
+        ij = WorkerInputJobStruct()
+        ij.program = program._handle().value
+        ij.h_input, ij.n_input = x.ctypes.data if x.size else None, x.size
+        ij.h_output, ij.output_cap = out.ctypes.data, out.size - 1
+        job = ij.job
+        job.kind, job.po2 = JOB_RECURSION_INPUT, p_po2 if po2 is None else po2
+        job.suite = p_suite if suite is None else (SUITES[suite] if isinstance(suite, str) else int(suite))
+        job.recursion = RecursionInput(None, None, 0, None, 0, None, 0, roots.ctypes.data if roots.size else None,
+                                       roots.size // 8)
+        return self._submit(job, 20, (ij, program, x, out, roots))
+
+    def output(self, ticket):
+        """Preflight.output of a kind-4 job that wait() has returned (kept for the last 256 such
+        jobs, until it is read)"""
+        return self.outputs.pop(ticket)
+
     def outstanding(self):
         """jobs submitted and not yet returned by wait()"""
         return len(self._pending)
@@ -1159,7 +1277,11 @@ class Worker:
         entry = self._pending.pop(done.value, None)
         if entry is None:
             raise R0HipError("r0hip_worker_wait returned a job this Worker did not submit")
-        job, seal, mix, _keep = entry
+        job, seal, mix, keep = entry
+        if job.kind == JOB_RECURSION_INPUT:
+            self.outputs[int(job.ticket)] = keep[3][: keep[0].n_output].copy()
+            while len(self.outputs) > 256:
+                self.outputs.pop(next(iter(self.outputs)))
         error = None
         if job.error:
             error = C.cast(job.error, C.c_char_p).value.decode()
