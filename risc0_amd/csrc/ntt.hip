@@ -17,6 +17,7 @@
 // upper passes read 2^c adjacent columns per workgroup so every global access is
 // a >=64-byte contiguous run. A po2=20 evaluate (L = 22) is two passes (13 + 9 bits): one read
 // of the coefficients and one read+write of the 4x domain through HBM.
+#include "ntt_bfly.h"
 #include "runtime.h"
 
 #include <map>
@@ -95,36 +96,11 @@ __device__ __forceinline__ void stage_group(uint32_t* lds, const uint32_t* tw, c
       if (FROM_EB) v[m] = csrc[(j << (B - FROM_EB)) + ((tb + m * h) >> FROM_EB)];  // replicated input
       else v[m] = lds[LIN ? base + m * step : lidx<COLS, B, C>(j, tb + m * h)];
     }
-    if (!INV) {
-#pragma unroll
-      for (uint32_t st = 0; st < NST; st++) {
-        const uint32_t half = 1u << st, hs = h << st;
-#pragma unroll
-        for (uint32_t m = 0; m < M; m++) {
-          if (m & half) continue;
-          // a group that starts at stage 1 has k = 0, so its twiddle w_{2^s}^0 = 1 wherever
-          // m & (half - 1) == 0 (all of stage 1, half of stage 2, a quarter of stage 3):
-          // no multiply, the staged words being canonical already
-          uint32_t x = v[m], y = v[m + half];
-          if (!(S0 == 1 && (m & (half - 1)) == 0)) y = fp_mul(y, tw[hs + k + (m & (half - 1)) * h]);
-          v[m] = fp_add(x, y);
-          v[m + half] = fp_sub(x, y);
-        }
-      }
-    } else {
-#pragma unroll
-      for (int st = NST - 1; st >= 0; st--) {
-        const uint32_t half = 1u << st, hs = h << st;
-#pragma unroll
-        for (uint32_t m = 0; m < M; m++) {
-          if (m & half) continue;
-          uint32_t x = v[m], y = v[m + half];
-          v[m] = fp_add(x, y);
-          v[m + half] = fp_sub(x, y);
-          if (!(S0 == 1 && (m & (half - 1)) == 0)) v[m + half] = fp_mul(v[m + half], tw[hs + k + (m & (half - 1)) * h]);
-        }
-      }
-    }
+    // a group that starts at stage 1 has k = 0, so its twiddle w_{2^s}^0 = 1 wherever
+    // m & (half - 1) == 0 (all of stage 1, half of stage 2, a quarter of stage 3): no
+    // multiply there. bfly_group leaves the words that only feed a twiddle multiply
+    // unreduced; what goes back to LDS is canonical.
+    bfly_group<NST, INV, S0 == 1>(v, [&](uint32_t st, uint32_t q) { return tw[(h << st) + k + q * h]; });
 #pragma unroll
     for (uint32_t m = 0; m < M; m++) lds[LIN ? base + m * step : lidx<COLS, B, C>(j, tb + m * h)] = v[m];
   }
@@ -191,13 +167,20 @@ struct ColTwiddles {
   // f(i, w) for every i < E with w = base * c^k, k = rev_{B-LR}(i), walking k in order: S
   // running products advance by c^S, so only S twiddles are live at a time (a table of all E
   // held 32 more VGPRs per lane in the B = 9 column pass: 165 VGPRs, 3 waves per SIMD)
-  template <typename F>
+  // f multiplies with w as the first operand of fp_mul_wide against a canonical data word,
+  // so w may be a lazy word (< 2p, ntt_bfly.h). LAZY: the running products skip their last
+  // fold; each is only ever the first operand of a fp_mul_wide*, against the canonical c or
+  // step here and in f. c and step multiply as second operands (and c enters fp_pow), so
+  // they stay canonical. The lazy form shifts the register allocation by 2-9 VGPRs, which
+  // costs the forward B = 7, 8 and the inverse B = 9 kernels a wave per SIMD, so the caller
+  // asks for it only where it is free (profiles/ntt_lazy_ab.txt).
+  template <bool LAZY, typename F>
   __device__ __forceinline__ static void apply(const PassArgs& p, uint32_t ex, uint32_t t0, F&& f) {
     const uint32_t c = fp_mul(p.sc_hi[ex >> p.sc_split], p.sc_lo[ex & ((1u << p.sc_split) - 1)]);
     uint32_t cur[S];
     cur[0] = fp_pow(c, uint64_t(bitrev_n(t0, LR)) << (B - LR));
 #pragma unroll
-    for (uint32_t k = 1; k < S; k++) cur[k] = fp_mul(cur[k - 1], c);
+    for (uint32_t k = 1; k < S; k++) cur[k] = LAZY ? fp_mul_wide_lazy(cur[k - 1], c) : fp_mul(cur[k - 1], c);
     uint32_t step = c;
 #pragma unroll
     for (uint32_t k = 1; k < S; k <<= 1) step = fp_mul(step, step);  // c^S
@@ -206,7 +189,7 @@ struct ColTwiddles {
 #pragma unroll
       for (uint32_t s = 0; s < S; s++) {
         f(bitrev_n(k0 + s, B - LR), cur[s]);
-        if (k0 + S < E) cur[s] = fp_mul(cur[s], step);
+        if (k0 + S < E) cur[s] = LAZY ? fp_mul_wide_lazy(cur[s], step) : fp_mul(cur[s], step);
       }
     }
   }
@@ -287,7 +270,7 @@ __global__ __launch_bounds__(NT) void ntt_pass_kernel(PassArgs p) {
       uint32_t v = p.in[(g_hi << (p.a + B)) + (uint64_t(t) << p.a) + low0 + j];
       if (!INV) {
         const uint32_t ex = (low0 + j) * bitrev_n(t, B);
-        v = fp_mul(v, fp_mul(p.sc_hi[ex >> p.sc_split], p.sc_lo[ex & ((1u << p.sc_split) - 1)]));
+        v = fp_mul_wide(fp_mul_wide_lazy(p.sc_hi[ex >> p.sc_split], p.sc_lo[ex & ((1u << p.sc_split) - 1)]), v);
       }
       lds[lidx<COLS, B, C>(j, t)] = v;
     }
@@ -305,7 +288,10 @@ __global__ __launch_bounds__(NT) void ntt_pass_kernel(PassArgs p) {
     uint32_t r[E];
 #pragma unroll
     for (uint32_t i = 0; i < E; i++) r[i] = *reinterpret_cast<const uint32_t*>(cbase + (off0 + i * ostep));
-    if (!INV) ColTwiddles<B, C>::apply(p, low0 + j, t0, [&](uint32_t i, uint32_t w) { r[i] = fp_mul(r[i], w); });
+    // w may be a lazy word (ColTwiddles), the loaded r[i] is canonical
+    if (!INV)
+      ColTwiddles<B, C>::template apply<(B >= 9)>(p, low0 + j, t0,
+                                                 [&](uint32_t i, uint32_t w) { r[i] = fp_mul_wide(w, r[i]); });
 #pragma unroll
     for (uint32_t i = 0; i < E; i++) lds[lidx<COLS, B, C>(j, R * i + t0)] = r[i];
   }
@@ -322,8 +308,8 @@ __global__ __launch_bounds__(NT) void ntt_pass_kernel(PassArgs p) {
     const uint32_t off0 = ((t0 << p.a) + j) * 4u, ostep = (R << p.a) * 4u;
     auto put = [&](uint32_t i, uint32_t v) { *reinterpret_cast<uint32_t*>(obase + (off0 + i * ostep)) = v; };
     if (INV) {
-      ColTwiddles<B, C>::apply(p, low0 + j, t0, [&](uint32_t i, uint32_t w) {
-        put(i, fp_mul(lds[lidx<COLS, B, C>(j, R * i + t0)], w));
+      ColTwiddles<B, C>::template apply<false>(p, low0 + j, t0, [&](uint32_t i, uint32_t w) {
+        put(i, fp_mul_wide(w, lds[lidx<COLS, B, C>(j, R * i + t0)]));
       });
     } else {
 #pragma unroll
@@ -349,14 +335,16 @@ __global__ __launch_bounds__(NT) void ntt_pass_kernel(PassArgs p) {
     uint32_t v = lds[lidx<COLS, B, C>(j, t)];
     if (INV && COLS) {
       const uint32_t ex = (low0 + j) * bitrev_n(t, B);
-      v = fp_mul(v, fp_mul(p.sc_hi[ex >> p.sc_split], p.sc_lo[ex & ((1u << p.sc_split) - 1)]));
+      v = fp_mul_wide(fp_mul_wide_lazy(p.sc_hi[ex >> p.sc_split], p.sc_lo[ex & ((1u << p.sc_split) - 1)]), v);
     }
     if (LAST) {
-      v = fp_mul(v, p.post_t[t]);
+      // a product that only feeds the next one keeps its lazy form (ntt_bfly.h)
       if (p.post_hi) {
         const uint64_t g = (wg << C) + j;
         const uint32_t row = uint32_t(g & ((uint64_t(1) << (p.L - B)) - 1));
-        v = fp_mul(v, p.post_hi[row]);
+        v = fp_mul_wide(fp_mul_wide_lazy(v, p.post_t[t]), p.post_hi[row]);
+      } else {
+        v = fp_mul(v, p.post_t[t]);
       }
     }
     p.out[e] = v;
@@ -404,7 +392,7 @@ __global__ __launch_bounds__(kThreads) void zk_shift_kernel(uint32_t* io, uint64
   for (uint64_t i = uint64_t(blockIdx.x) * kThreads + threadIdx.x; i < n; i += uint64_t(gridDim.x) * kThreads) {
     uint32_t pos = uint32_t(i & ((uint64_t(1) << L) - 1));
     uint32_t lo = pos & ((1u << h) - 1), hi = pos >> h;
-    io[i] = fp_mul(io[i], fp_mul(A[bitrev_n(lo, h)], B[bitrev_n(hi, L - h)]));
+    io[i] = fp_mul_wide(fp_mul_wide_lazy(A[bitrev_n(lo, h)], B[bitrev_n(hi, L - h)]), io[i]);
   }
 }
 
