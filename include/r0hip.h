@@ -675,7 +675,11 @@ const char* r0hip_prove_segments(const char* circuit, int suite, uint32_t po2, i
  * host thread while the GPU proves the next jobs, as ProverImpl::prove_segment_core verifies a
  * receipt before returning it (zkvm/src/host/server/prove/prover_impl.rs:262-280); a seal that
  * fails sets that job's error ("receipt verification failed: ...") and the other jobs still
- * return. Host arrays must stay valid until the call returns. */
+ * return. verify == R0HIP_VERIFY_RECEIPTS_DEVICE (2), here and in r0hip_worker_create: the same
+ * check through r0hip_verify_seal_on(R0HIP_VERIFY_DEVICE, ...), the seal's Merkle openings hashed
+ * on the verifier thread's own stream; every other nonzero value is the host check.
+ * Host arrays must stay valid until the call returns. */
+#define R0HIP_VERIFY_RECEIPTS_DEVICE 2
 typedef struct r0hip_trace_input {
   uint32_t mode;                      /* as r0hip_rv32im_witgen */
   const uint32_t* h_global;           /* build_global_vec's 90 Montgomery words */
@@ -847,6 +851,52 @@ const char* r0hip_verify_seal(const char* circuit, int suite, const uint32_t* se
 /* [host-only] */
 const char* r0hip_testing_verify_seal_structure(const char* circuit, int suite, const uint32_t* seal,
                                                 size_t seal_len, uint32_t* po2_out);
+/* ---- the same check with the Merkle openings hashed on the device (opt-in) ----
+ * where = R0HIP_VERIFY_HOST is r0hip_verify_seal itself: host-only, no GPU, no r0hip_init.
+ * where = R0HIP_VERIFY_DEVICE keeps the transcript, the trees' top layers, the validity equation
+ * and the FRI arithmetic on the host and hashes the seal's deferred openings (each row hash and
+ * its path, 200-350 per seal) in one kernel on the calling thread's stream: the seal goes up once
+ * through the thread's page-locked staging arena, the opening table and the results come from the
+ * thread's pool, and the host compares each result with the tree's top layer, so the device
+ * never decides a verdict. Verdicts, messages (the first failure in opening order), *po2_out and
+ * the code root are those of the host check. Poseidon2 and SHA-256 run on the device;
+ * Poseidon254 (suite 2) is accepted and runs the host openings, since a BN254 permutation per
+ * lane has no measured device form. The device call always drains (also in deferred mode) and
+ * the thread keeps no device memory afterwards. Any other `where` is an error. */
+#define R0HIP_VERIFY_HOST 0
+#define R0HIP_VERIFY_DEVICE 1
+/* [drains] */
+const char* r0hip_verify_seal_on(int where, const char* circuit, int suite, const uint32_t* seal, size_t seal_len,
+                                 const uint32_t* h_code_roots, size_t n_code_roots, uint32_t* h_code_root_out,
+                                 uint32_t* po2_out);
+/* TESTING ONLY, as r0hip_testing_verify_seal_structure is, with the openings host or device. */
+/* [drains] */
+const char* r0hip_testing_verify_seal_structure_on(int where, const char* circuit, int suite, const uint32_t* seal,
+                                                   size_t seal_len, uint32_t* po2_out);
+/* The device step by itself: for each of n_open openings over the word buffer h_words (n_words
+ * words), cur = hash_elems(suite, h_words + row_off, cols), then `levels` times cur =
+ * hash_pair(other, cur) or hash_pair(cur, other) with `other` the next 8 words from h_words +
+ * path_off: `other` goes left when the running index (index, then index >> 1, ...) is odd. index
+ * is the leaf's heap index (row + rows of the tree). h_digests gets cur (8 words per opening),
+ * h_status one word per opening: 0 computed; 2 (Poseidon2 only) a path digest word is >= p, the
+ * case the verifier rejects as "non-canonical Poseidon2 digest word in seal" (the digest is then
+ * written as zeros; the other openings are unaffected). The digests are byte for byte the host
+ * verifier's (Poseidon2: sponge of rate 16, unpadded; SHA-256: the unpadded row hash over
+ * little-endian words). suite 0 or 1; suite 2 has no device form and is an error here. Refused
+ * on the host before any device call, naming the argument: a NULL array with a nonzero count,
+ * cols outside [1, 256], levels above 40, a row or path range outside n_words, and (Poseidon2)
+ * a row word >= p. Ranges may overlap and openings may share rows. */
+typedef struct r0hip_opening {
+  uint64_t row_off;  /* first word of the row in h_words */
+  uint64_t path_off; /* first word of the path: 8 words per level */
+  uint64_t index;    /* heap index of the leaf */
+  uint32_t cols;     /* row length in words, 1..256 */
+  uint32_t levels;   /* path length in digests, 0..40 */
+} r0hip_opening;
+/* [drains] */
+const char* r0hip_merkle_open_digests(int suite, const uint32_t* h_words, size_t n_words, const r0hip_opening* h_open,
+                                      size_t n_open, uint32_t* h_digests, uint32_t* h_status);
+
 /* PolyExt::poly_ext of the circuit (its generated poly_ext.rs, called at mod.rs:356-386): the
  * constraint polynomial at the out-of-domain point. h_mix (mix_size) and h_global
  * (output_size) are Montgomery words, h_eval_u one FpExt (4 words) per tap in tap order,

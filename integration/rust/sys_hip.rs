@@ -206,6 +206,24 @@ pub struct R0HipRecursionInputInfo {
     pub plan_host_bytes: u64,
 }
 
+/// One Merkle opening over a word buffer (struct r0hip_opening): the row at `row_off`, `levels`
+/// path digests at `path_off`, sides read from the leaf's heap index.
+#[repr(C)]
+pub struct R0HipOpening {
+    pub row_off: u64,
+    pub path_off: u64,
+    pub index: u64,
+    pub cols: u32,
+    pub levels: u32,
+}
+
+/// `where` of r0hip_verify_seal_on: the openings on host threads, or hashed on the device.
+pub const R0HIP_VERIFY_HOST: c_int = 0;
+pub const R0HIP_VERIFY_DEVICE: c_int = 1;
+/// `verify` of r0hip_prove_trace_segments and r0hip_worker_create: receipts checked with the
+/// openings on the device (any other nonzero value: on the host).
+pub const R0HIP_VERIFY_RECEIPTS_DEVICE: c_int = 2;
+
 #[link(name = "r0hip")]
 unsafe extern "C" {
     // ---- device and memory (cust's role in hal/cuda.rs:235-421) ----
@@ -664,6 +682,35 @@ unsafe extern "C" {
         seal: *const u32,
         seal_len: usize,
         po2_out: *mut u32,
+    ) -> *const c_char;
+    // ---- verification with the Merkle openings on the device (opt-in; `where_` is the C `where`) ----
+    pub fn r0hip_verify_seal_on(
+        where_: c_int,
+        circuit: *const c_char,
+        suite: c_int,
+        seal: *const u32,
+        seal_len: usize,
+        h_code_roots: *const u32,
+        n_code_roots: usize,
+        h_code_root_out: *mut u32,
+        po2_out: *mut u32,
+    ) -> *const c_char;
+    pub fn r0hip_testing_verify_seal_structure_on(
+        where_: c_int,
+        circuit: *const c_char,
+        suite: c_int,
+        seal: *const u32,
+        seal_len: usize,
+        po2_out: *mut u32,
+    ) -> *const c_char;
+    pub fn r0hip_merkle_open_digests(
+        suite: c_int,
+        h_words: *const u32,
+        n_words: usize,
+        h_open: *const R0HipOpening,
+        n_open: usize,
+        h_digests: *mut u32,
+        h_status: *mut u32,
     ) -> *const c_char;
     pub fn r0hip_poly_ext(
         circuit: *const c_char,

@@ -6,18 +6,24 @@
 //               sponge; sha/cpu.rs:56-77 unpadded SHA-256 over LE word bytes)
 //   hash_fold : cpu.rs:569-581 -> HashFn::hash_pair (poseidon2/mod.rs:47-59;
 //               sha/mod.rs:96-98 single compression from the IV)
+//   merkle_open : the verifier's openings (verify/merkle.rs:159-186), a row hash and its path
+//               per work item, for the opt-in device receipt check (latency-shaped: below)
 // One lane hashes one row: consecutive lanes read consecutive rows of each
 // column, so every column read is a fully coalesced 256-byte wave access; the
 // 24-cell state lives in VGPRs. Poseidon2 is integer-VALU bound (~1.4k modmul per
 // permutation), not HBM bound.
+#include "../../include/r0hip.h"
+#include "devmem.h"
 #include "poseidon2.h"
 #include "poseidon254.h"
 #include "runtime.h"
 #include "transcript.h"
 
+#include <cstring>
 #include <map>
 #include <mutex>
 #include <tuple>
+#include <vector>
 
 namespace r0 {
 namespace {
@@ -464,6 +470,152 @@ __global__ __launch_bounds__(kThreads) void fold_top_kernel(uint32_t* io, uint32
   }
 }
 
+// ---- a seal's Merkle openings (verify/merkle.rs:159-186 up to the comparison) -----------
+// Per opening: cur = hash_elems(row, cols), then per path level cur = hash_pair of cur and the
+// path digest, the side taken from the running heap index. A seal has a few hundred openings
+// and each is a dependent chain of 20-30 permutations, so the work is latency, not throughput:
+// one wave per workgroup spreads the waves over the CUs, and Poseidon2 runs one opening per
+// lane quad (poseidon2_mix_quad, a third of the per-lane dependent instructions). The quads of
+// a wave loop over their own block and level counts; the DPP moves of the permutation stay
+// inside a quad, whose four lanes share an opening and so are always active together. Every
+// range was checked on the host (merkle_open): cols <= 256, levels <= 40, rows and paths inside
+// `words`. Output: 8 digest words per opening at out, one status word per opening at status
+// (0 computed; 2 Poseidon2 path digest word >= p, digest written as zeros).
+constexpr int kOpenThreads = 64;
+
+__global__ __launch_bounds__(kOpenThreads) void merkle_open_p2_quad_kernel(uint32_t* out, uint32_t* status,
+                                                                         const uint32_t* __restrict__ words,
+                                                                         const r0hip_opening* __restrict__ open,
+                                                                         uint32_t n_open) {
+  const uint32_t i = (blockIdx.x * kOpenThreads + threadIdx.x) >> 2;
+  if (i >= n_open) return;  // whole quads
+  const uint32_t q = threadIdx.x & 3;
+  const r0hip_opening o = open[i];
+  const uint32_t* row = words + o.row_off;
+  const uint32_t* path = words + o.path_off;
+  // lane q holds cells 4j + q: rate cells j < 4 take row words 16b + 4j + q, the capacity
+  // (j = 4, 5) carries over; the next block's words load while this one is permuted
+  uint32_t c[6] = {0, 0, 0, 0, 0, 0}, nxt[4];
+  auto load = [&](uint32_t col) {
+#pragma unroll
+    for (int j = 0; j < 4; j++) nxt[j] = col + 4 * j + q < o.cols ? row[col + 4 * j + q] : 0u;
+  };
+  const uint32_t nblk = (o.cols + 15) / 16;
+  load(0);
+  uint32_t p0 = 0, p1 = 0;  // this lane's words q and 4 + q of the next path digest
+  for (uint32_t b = 0; b < nblk; b++) {
+#pragma unroll
+    for (int j = 0; j < 4; j++) c[j] = nxt[j];
+    if (b + 1 < nblk) load((b + 1) * 16);
+    else if (o.levels) p0 = path[q], p1 = path[4 + q];
+    poseidon2_mix_quad(c);
+  }
+  uint64_t idx = o.index;
+  uint32_t bad = 0;
+  for (uint32_t l = 0; l < o.levels; l++) {
+    const uint32_t o0 = p0, o1 = p1;
+    if (l + 1 < o.levels) p0 = path[8 * (l + 1) + q], p1 = path[8 * (l + 1) + 4 + q];
+    bad |= uint32_t(o0 >= kP) | uint32_t(o1 >= kP);
+    const bool low = idx & 1;
+    idx >>= 1;
+    const uint32_t c0 = c[0], c1 = c[1];  // digest words q and 4 + q
+    c[0] = low ? o0 : c0;
+    c[1] = low ? o1 : c1;
+    c[2] = low ? c0 : o0;
+    c[3] = low ? c1 : o1;
+    c[4] = c[5] = 0;
+    poseidon2_mix_quad(c);
+  }
+  bad |= p2q_dpp(bad, 1);
+  bad |= p2q_dpp(bad, 2);
+  out[uint64_t(i) * 8 + q] = bad ? 0u : c[0];
+  out[uint64_t(i) * 8 + 4 + q] = bad ? 0u : c[1];
+  if (q == 0) status[i] = bad ? 2u : 0u;
+}
+
+// The same with one opening per lane on the row kernels' poseidon2_mix (R0_MERKLE_OPEN_QUAD=0):
+// the form the quad kernel is measured against (tools/bench_verify_openings.py).
+__global__ __launch_bounds__(kOpenThreads) void merkle_open_p2_lane_kernel(uint32_t* out, uint32_t* status,
+                                                                         const uint32_t* __restrict__ words,
+                                                                         const r0hip_opening* __restrict__ open,
+                                                                         uint32_t n_open) {
+  const uint32_t i = blockIdx.x * kOpenThreads + threadIdx.x;
+  if (i >= n_open) return;
+  const r0hip_opening o = open[i];
+  const uint32_t* row = words + o.row_off;
+  const uint32_t* path = words + o.path_off;
+  uint32_t c[24];
+#pragma unroll
+  for (int k = 0; k < 24; k++) c[k] = 0;
+#pragma unroll 1
+  for (uint32_t col = 0; col < o.cols; col += 16) {
+#pragma unroll
+    for (int k = 0; k < 16; k++) c[k] = col + k < o.cols ? row[col + k] : 0u;
+    poseidon2_mix(c);
+  }
+  uint64_t idx = o.index;
+  uint32_t bad = 0;
+#pragma unroll 1
+  for (uint32_t l = 0; l < o.levels; l++) {
+    const bool low = idx & 1;
+    idx >>= 1;
+#pragma unroll
+    for (int k = 0; k < 8; k++) {
+      const uint32_t w = path[8 * l + k], cur = c[k];
+      bad |= uint32_t(w >= kP);
+      c[k] = low ? w : cur;
+      c[8 + k] = low ? cur : w;
+      c[16 + k] = 0;
+    }
+    poseidon2_mix(c);
+  }
+#pragma unroll
+  for (int k = 0; k < 8; k++) out[uint64_t(i) * 8 + k] = bad ? 0u : c[k];
+  status[i] = bad ? 2u : 0u;
+}
+
+// SHA-256: one opening per lane (a compression is ~3k dependent instructions whichever way it
+// is cut). Any 32-bit word is a legal digest word here, so the status is always 0.
+__global__ __launch_bounds__(kOpenThreads) void merkle_open_sha_kernel(uint32_t* out, uint32_t* status,
+                                                                     const uint32_t* __restrict__ words,
+                                                                     const r0hip_opening* __restrict__ open,
+                                                                     uint32_t n_open) {
+  const uint32_t i = blockIdx.x * kOpenThreads + threadIdx.x;
+  if (i >= n_open) return;
+  const r0hip_opening o = open[i];
+  const uint32_t* row = words + o.row_off;
+  const uint32_t* path = words + o.path_off;
+  uint32_t s[8], w[16], cur[8];
+  sha_init(s);
+#pragma unroll 1
+  for (uint32_t col = 0; col < o.cols; col += 16) {
+#pragma unroll
+    for (int k = 0; k < 16; k++) w[k] = col + k < o.cols ? __builtin_bswap32(row[col + k]) : 0u;
+    sha_compress(s, w);
+  }
+#pragma unroll
+  for (int k = 0; k < 8; k++) cur[k] = s[k];  // big-endian state words: the digest before its bswap
+  uint64_t idx = o.index;
+#pragma unroll 1
+  for (uint32_t l = 0; l < o.levels; l++) {
+    const bool low = idx & 1;
+    idx >>= 1;
+#pragma unroll
+    for (int k = 0; k < 8; k++) {
+      const uint32_t other = __builtin_bswap32(path[8 * l + k]);
+      w[k] = low ? other : cur[k];
+      w[8 + k] = low ? cur[k] : other;
+    }
+    sha_init(s);
+    sha_compress(s, w);
+#pragma unroll
+    for (int k = 0; k < 8; k++) cur[k] = s[k];
+  }
+#pragma unroll
+  for (int k = 0; k < 8; k++) out[uint64_t(i) * 8 + k] = __builtin_bswap32(cur[k]);
+  status[i] = 0;
+}
+
 }  // namespace
 
 // Z_0 .. Z_levels for rows of `cols` columns ((levels + 1) * 8 words, cached): Z_0 is
@@ -714,6 +866,75 @@ void merkle_layers(hipStream_t s, int suite, uint32_t* nodes, size_t rows, size_
     else hipLaunchKernelGGL(fold_top_kernel<2>, grid, block, 0, s, nodes, uint32_t(layer), nullptr, 0u);
     HIP_OK(hipGetLastError());
   }
+}
+
+// ---- Merkle openings of a seal (the kernels above) ----
+// Everything the kernels' loops and addresses depend on, checked on the host: a table that
+// passes can neither read outside [0, n_words) nor run longer than 16 + 40 hashes per opening.
+void merkle_open_check(int suite, size_t n_words, const r0hip_opening* h_open, size_t n_open) {
+  R0_REQUIRE(suite == 0 || suite == 1, "merkle_open: suite " + std::to_string(suite) +
+                                           " has no device form (Poseidon2 and SHA-256 only)");
+  R0_REQUIRE(n_open < (size_t(1) << 24), "merkle_open: n_open = " + std::to_string(n_open) + " is too large");
+  R0_REQUIRE(h_open || n_open == 0, "merkle_open: h_open is NULL");
+  for (size_t i = 0; i < n_open; i++) {
+    const r0hip_opening& o = h_open[i];
+    auto at = [&](const char* f) { return "merkle_open: h_open[" + std::to_string(i) + "]." + f; };
+    R0_REQUIRE(o.cols >= 1 && o.cols <= kMerkleOpenMaxCols,
+               at("cols") + " = " + std::to_string(o.cols) + " is outside [1, " + std::to_string(kMerkleOpenMaxCols) + "]");
+    R0_REQUIRE(o.levels <= kMerkleOpenMaxLevels,
+               at("levels") + " = " + std::to_string(o.levels) + " is above " + std::to_string(kMerkleOpenMaxLevels));
+    R0_REQUIRE(o.row_off <= n_words && o.cols <= n_words - o.row_off,
+               at("row_off") + ": the row [" + std::to_string(o.row_off) + ", +" + std::to_string(o.cols) +
+                   ") is outside n_words = " + std::to_string(n_words));
+    R0_REQUIRE(o.path_off <= n_words && size_t(o.levels) * 8 <= n_words - o.path_off,
+               at("path_off") + ": the path [" + std::to_string(o.path_off) + ", +" + std::to_string(o.levels * 8) +
+                   ") is outside n_words = " + std::to_string(n_words));
+  }
+}
+
+// Poseidon2 openings one per lane quad; R0_MERKLE_OPEN_QUAD=0 selects one per lane. Read at each
+// launch (one per receipt), so tools/bench_verify_openings.py alternates the two in one process.
+static bool open_quad() { return env_size("R0_MERKLE_OPEN_QUAD", 1) != 0; }
+
+void merkle_open(hipStream_t s, int suite, const uint32_t* d_words, size_t n_words, const r0hip_opening* h_open,
+                 size_t n_open, r0hip_opening* d_open, uint32_t* d_out) {
+  merkle_open_check(suite, n_words, h_open, n_open);
+  if (n_open == 0) return;
+  R0_REQUIRE(d_words && d_open && d_out, "merkle_open: null device pointer");
+  upload_async(d_open, h_open, n_open * sizeof(r0hip_opening));
+  double hashes = 0, bytes = 0;
+  for (size_t i = 0; i < n_open; i++) {
+    hashes += (h_open[i].cols + 15) / 16 + h_open[i].levels;
+    bytes += 4.0 * h_open[i].cols + 32.0 * h_open[i].levels + 36 + sizeof(r0hip_opening);
+  }
+  KScope ks(suite == 0 ? "merkle_open_poseidon2" : "merkle_open_sha256", bytes, suite == 0 ? hashes * kP2Modmuls : 0);
+  uint32_t* d_status = d_out + n_open * 8;
+  const dim3 block(kOpenThreads);
+  const uint32_t n = uint32_t(n_open);
+  if (suite == 0 && open_quad())
+    hipLaunchKernelGGL(merkle_open_p2_quad_kernel, dim3(div_up(4 * n_open, kOpenThreads)), block, 0, s, d_out, d_status,
+                       d_words, d_open, n);
+  else if (suite == 0)
+    hipLaunchKernelGGL(merkle_open_p2_lane_kernel, dim3(div_up(n_open, kOpenThreads)), block, 0, s, d_out, d_status,
+                       d_words, d_open, n);
+  else
+    hipLaunchKernelGGL(merkle_open_sha_kernel, dim3(div_up(n_open, kOpenThreads)), block, 0, s, d_out, d_status,
+                       d_words, d_open, n);
+  HIP_OK(hipGetLastError());
+}
+
+void merkle_open_host(int suite, const uint32_t* h_words, size_t n_words, const r0hip_opening* h_open, size_t n_open,
+                      uint32_t* h_digests, uint32_t* h_status) {
+  merkle_open_check(suite, n_words, h_open, n_open);  // before the first device call
+  if (n_open == 0) return;
+  DevBuf words(n_words), table(n_open * (sizeof(r0hip_opening) / 4)), out(n_open * 9);
+  upload_async(words.p, h_words, n_words * 4);
+  merkle_open(stream(), suite, words.p, n_words, h_open, n_open, reinterpret_cast<r0hip_opening*>(table.p), out.p);
+  std::vector<uint32_t> got(n_open * 9);
+  download(got.data(), out.p, got.size() * 4);
+  memcpy(h_digests, got.data(), n_open * 32);
+  memcpy(h_status, got.data() + n_open * 8, n_open * 4);
+  stage_reset();  // the stream is drained: the arena's staged seal and table are free again
 }
 
 }  // namespace r0

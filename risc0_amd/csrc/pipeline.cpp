@@ -232,6 +232,16 @@ void check_backs_trace(const r0hip_trace_input& t, const std::string& who) {
              who + ": trace job: null trace array with a nonzero count");
 }
 
+// The verifier threads' receipt check: r0hip_verify_seal, or with verify ==
+// R0HIP_VERIFY_RECEIPTS_DEVICE the same check with the seal's openings hashed on the device.
+const char* check_receipt(int verify, const char* circuit, int suite, const std::vector<uint32_t>& seal,
+                          const uint32_t* roots, size_t n_roots, uint32_t* po2) {
+  if (verify == R0HIP_VERIFY_RECEIPTS_DEVICE)
+    return r0hip_verify_seal_on(R0HIP_VERIFY_DEVICE, circuit, suite, seal.data(), seal.size(), roots, n_roots, nullptr,
+                                po2);
+  return r0hip_verify_seal(circuit, suite, seal.data(), seal.size(), roots, n_roots, nullptr, po2);
+}
+
 // Trace jobs: the uploader copies job i's trace into a free trace set and hands the set to a
 // prover at once; the prover allocates its witness groups and queues their fill (which reads no
 // input), then waits on the host until the uploader has queued the set's copies and makes its
@@ -241,8 +251,10 @@ void check_backs_trace(const r0hip_trace_input& t, const std::string& who) {
 // verify: each finished seal is checked by r0hip_verify_seal (the validity equation included) on
 // a host thread of its own while the GPU proves the next segments, as ProverImpl::
 // prove_segment_core verifies a receipt before it returns it (zkvm/src/host/server/prove/
-// prover_impl.rs:262-280); a seal that fails fails its job.
-const char* prove_trace_jobs(int suite, uint32_t po2, r0hip_trace_job* jobs, size_t njobs, size_t k, bool verify) {
+// prover_impl.rs:262-280); a seal that fails fails its job. verify == R0HIP_VERIFY_RECEIPTS_DEVICE:
+// the same check with the openings hashed on the device (check_receipt), on the verifier thread's
+// own stream, which it gets the thread-local way at its first seal.
+const char* prove_trace_jobs(int suite, uint32_t po2, r0hip_trace_job* jobs, size_t njobs, size_t k, int verify) {
   const size_t n = size_t(1) << po2;
   size_t cap_inj = 1, cap_txn = 1, cap_big = 4;
   for (size_t i = 0; i < njobs; i++) {
@@ -320,8 +332,7 @@ const char* prove_trace_jobs(int suite, uint32_t po2, r0hip_trace_job* jobs, siz
         r0hip_trace_job& j = jobs[item.first];
         const auto t0 = std::chrono::steady_clock::now();
         uint32_t got = 0;
-        const char* err = r0hip_verify_seal("rv32im", suite, item.second.data(), item.second.size(), nullptr, 0,
-                                            nullptr, &got);
+        const char* err = check_receipt(verify, "rv32im", suite, item.second, nullptr, 0, &got);
         j.verify_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
         if (!err && got != po2) err = dup_msg("the seal is of another segment size");
         std::lock_guard<std::mutex> lk(vmu);
@@ -452,7 +463,7 @@ inline bool job_holds_program(const r0hip_worker_job* j) {
 struct WorkerImpl {
   uint32_t max_po2 = 0;
   size_t k = 0;
-  bool verify = false;
+  int verify = 0;  // r0hip_worker_create's: 0 none, R0HIP_VERIFY_RECEIPTS_DEVICE device openings, else host
   uint32_t key[8] = {};
   std::vector<WorkerSet> sets;
   Queue free_q, ready_q;
@@ -711,8 +722,7 @@ struct WorkerImpl {
         roots = recursion_program_shape(job_program(j)).control_id;
         n_roots = 1;
       }
-      const char* err = r0hip_verify_seal(rec ? "recursion" : "rv32im", j->suite, item.second.data(),
-                                          item.second.size(), roots, n_roots, nullptr, &got);
+      const char* err = check_receipt(verify, rec ? "recursion" : "rv32im", j->suite, item.second, roots, n_roots, &got);
       j->verify_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
       if (!err && got != j->po2) err = dup_msg("the seal is of another segment size");
       if (err) {
@@ -939,7 +949,7 @@ extern "C" const char* r0hip_prove_trace_segments(int suite, uint32_t po2, r0hip
     }
     if (njobs) {
       const size_t k = std::max<size_t>(1, std::min<size_t>(in_flight ? in_flight : 2, njobs));
-      err = prove_trace_jobs(suite, po2, jobs, njobs, k, verify != 0);
+      err = prove_trace_jobs(suite, po2, jobs, njobs, k, verify);
     }
   } catch (const std::exception& e) {
     err = dup_msg(e.what());
@@ -984,7 +994,7 @@ extern "C" const char* r0hip_worker_create(r0hip_worker** out, uint32_t max_po2,
     WorkerImpl& m = w->impl;
     m.max_po2 = max_po2;
     m.k = in_flight ? in_flight : 2;
-    m.verify = verify != 0;
+    m.verify = verify;
     if (h_noise_key) memcpy(m.key, h_noise_key, sizeof m.key);
     else os_random_key(m.key);
     const size_t n = size_t(1) << max_po2;

@@ -15,6 +15,7 @@
 
 struct r0hip_bigint_back;  // include/r0hip.h
 struct r0hip_recursion_program;
+struct r0hip_opening;
 
 #define HIP_OK(expr)                                                                          \
   do {                                                                                        \
@@ -301,6 +302,21 @@ void merkle_tree(hipStream_t s, int suite, uint32_t* nodes, const uint32_t* matr
 // The layers above leaves already in nodes[rows..2rows). `cols` (the matrix's column count,
 // SIZE_MAX if unknown) lets Poseidon2 and SHA-256 layers skip zero subtrees (hash.hip, ZeroSub).
 void merkle_layers(hipStream_t s, int suite, uint32_t* nodes, size_t rows, size_t cols = SIZE_MAX);
+// A seal's Merkle openings up to the comparison with the tree (MerkleVerifier::check, verify_core.h):
+// per opening, hash_elems of the row at words[row_off .. + cols), then `levels` pair hashes with the
+// path digests at words[path_off ..], sides from the heap index. Suites 0 and 1. The launcher
+// checks the host copy of the table (merkle_open_check: cols in [1, 256], levels <= 40, every range
+// inside n_words; throws before any device call), uploads it to d_open and queues one kernel on s:
+// d_out gets 8 digest words per opening, then one status word per opening (0 computed, 2 a
+// Poseidon2 path digest word >= p). Poseidon2 row words must be canonical (< p).
+constexpr uint32_t kMerkleOpenMaxCols = 256, kMerkleOpenMaxLevels = 40;
+void merkle_open_check(int suite, size_t n_words, const r0hip_opening* h_open, size_t n_open);
+void merkle_open(hipStream_t s, int suite, const uint32_t* d_words, size_t n_words, const r0hip_opening* h_open,
+                 size_t n_open, r0hip_opening* d_open, uint32_t* d_out);
+// Host arrays in and out on the calling thread's stream, complete on return: the words go up
+// once through the thread's staging arena, the table and the outputs come from its pool.
+void merkle_open_host(int suite, const uint32_t* h_words, size_t n_words, const r0hip_opening* h_open, size_t n_open,
+                      uint32_t* h_digests, uint32_t* h_status);
 
 // Element-wise and polynomial kernels (eltwise.hip).
 void eltwise_add(hipStream_t s, uint32_t* out, const uint32_t* a, const uint32_t* b, size_t n);

@@ -11,7 +11,9 @@
 // the root must be in it. Field words in the seal must be canonical (read_field_elem_slice).
 // r0hip_testing_verify_seal_structure skips the validity equation for seals of synthetic
 // witnesses, which do not satisfy the constraints; it is for tests, never for receipts.
-// Host code only — no HIP call, so it runs without a GPU.
+// Host code only — no HIP call, so it runs without a GPU; the one exception is opt-in:
+// r0hip_verify_seal_on(R0HIP_VERIFY_DEVICE, ...) hands the deferred Merkle openings to the device
+// (device_openings below), everything else of the check staying here.
 #include <cstdlib>
 #include <cstring>
 #include <stdexcept>
@@ -58,8 +60,34 @@ FpExt poly_ext(const CircuitDef& c, const uint32_t* mix, const uint32_t* global,
 namespace {
 using namespace vfy;
 
+// The device opening backend (r0hip_verify_seal_on with R0HIP_VERIFY_DEVICE): the pending list as
+// an r0hip_opening table over the seal words, hashed by merkle_open_host on the calling thread's
+// stream. The launcher checks every range again and refuses on the host.
+void device_openings(int suite, const uint32_t* words, size_t n_words, const std::vector<PendingOpening>& pending,
+                     OpeningResult* out) {
+  const size_t n = pending.size();
+  std::vector<r0hip_opening> table(n);
+  for (size_t i = 0; i < n; i++) {
+    const PendingOpening& p = pending[i];
+    table[i].row_off = uint64_t(p.row - words);
+    table[i].path_off = uint64_t(p.path - words);
+    table[i].index = uint64_t(p.idx) + p.tree->rows;
+    R0_REQUIRE(p.tree->cols <= kMerkleOpenMaxCols, "merkle_open: a group of " + std::to_string(p.tree->cols) +
+                                                       " columns is wider than the device openings take");
+    table[i].cols = uint32_t(p.tree->cols);
+    table[i].levels = uint32_t(p.tree->path_levels(p.idx));
+  }
+  std::vector<uint32_t> digests(n * 8), status(n);
+  merkle_open_host(suite, words, n_words, table.data(), n, digests.data(), status.data());
+  for (size_t i = 0; i < n; i++) {
+    out[i].cur = digest_of(&digests[8 * i]);
+    out[i].status = status[i];
+  }
+}
+
 uint32_t verify_seal(const CircuitDef& c, int suite, const uint32_t* seal, size_t len, bool check_validity,
-                     const uint32_t* code_roots, size_t n_code_roots, uint32_t* code_root_out) {
+                     const uint32_t* code_roots, size_t n_code_roots, uint32_t* code_root_out,
+                     OpeningBackend backend = nullptr) {
   if (c.name == std::string("rv32im")) {  // rv32im/src/lib.rs:78-92: a version word leads the seal
     if (len < 1 || seal[0] != 2) throw VerifyError("bad rv32im seal version");
     seal++;
@@ -67,6 +95,7 @@ uint32_t verify_seal(const CircuitDef& c, int suite, const uint32_t* seal, size_
   }
   ReadIOP iop(seal, len, suite);
   iop.defer = true;  // openings hashed after the transcript, on several threads (check_pending)
+  iop.backend = backend;  // or in one device launch
   uint32_t psi[16], ci[16];
   for (int i = 0; i < 16; i++) {
     psi[i] = fp_encode(uint8_t(PROOF_SYSTEM_INFO[i]));
@@ -108,14 +137,15 @@ using namespace r0;
 
 static const char* verify_entry(const char* circuit, int suite, const uint32_t* seal, size_t seal_len,
                                 bool check_validity, const uint32_t* code_roots, size_t n_code_roots,
-                                uint32_t* code_root_out, uint32_t* po2_out) {
+                                uint32_t* code_root_out, uint32_t* po2_out, vfy::OpeningBackend backend = nullptr) {
   try {
     const CircuitDef* c = find_circuit(circuit ? circuit : "");
     R0_REQUIRE(c, std::string("unknown circuit ") + (circuit ? circuit : "(null)"));
     R0_REQUIRE(suite >= 0 && suite <= 2, "unknown hash suite");
     R0_REQUIRE(seal || seal_len == 0, "seal is NULL");
     R0_REQUIRE(code_roots || n_code_roots == 0, "code_roots is NULL");
-    uint32_t po2 = verify_seal(*c, suite, seal, seal_len, check_validity, code_roots, n_code_roots, code_root_out);
+    uint32_t po2 =
+        verify_seal(*c, suite, seal, seal_len, check_validity, code_roots, n_code_roots, code_root_out, backend);
     if (po2_out) *po2_out = po2;
     return nullptr;
   } catch (const std::exception& e) {
@@ -134,6 +164,39 @@ extern "C" const char* r0hip_verify_seal(const char* circuit, int suite, const u
 extern "C" const char* r0hip_testing_verify_seal_structure(const char* circuit, int suite, const uint32_t* seal,
                                                            size_t seal_len, uint32_t* po2_out) {
   return verify_entry(circuit, suite, seal, seal_len, false, nullptr, 0, nullptr, po2_out);
+}
+
+// where = DEVICE: the host check with the device opening backend. Poseidon254 keeps the host
+// openings (no device form). The call drains and hands the thread's memory back, as every entry
+// point that gives the host a verdict does (api.cpp wrap); nothing here creates a stream on a
+// path that launches nothing.
+static const char* verify_entry_on(int where, const char* circuit, int suite, const uint32_t* seal, size_t seal_len,
+                                   bool check_validity, const uint32_t* code_roots, size_t n_code_roots,
+                                   uint32_t* code_root_out, uint32_t* po2_out) {
+  if (where == R0HIP_VERIFY_HOST)
+    return verify_entry(circuit, suite, seal, seal_len, check_validity, code_roots, n_code_roots, code_root_out, po2_out);
+  if (where != R0HIP_VERIFY_DEVICE)
+    return strdup(("r0hip: where = " + std::to_string(where) + " is neither R0HIP_VERIFY_HOST nor R0HIP_VERIFY_DEVICE")
+                      .c_str());
+  const char* err = verify_entry(circuit, suite, seal, seal_len, check_validity, code_roots, n_code_roots,
+                                 code_root_out, po2_out, suite == 2 ? nullptr : device_openings);
+  drain_after_error();  // a throw may have left work queued; a clean return has drained already
+  call_drained();
+  release_thread_memory();
+  return err;
+}
+
+extern "C" const char* r0hip_verify_seal_on(int where, const char* circuit, int suite, const uint32_t* seal,
+                                            size_t seal_len, const uint32_t* h_code_roots, size_t n_code_roots,
+                                            uint32_t* h_code_root_out, uint32_t* po2_out) {
+  return verify_entry_on(where, circuit, suite, seal, seal_len, true, h_code_roots, n_code_roots, h_code_root_out,
+                         po2_out);
+}
+
+extern "C" const char* r0hip_testing_verify_seal_structure_on(int where, const char* circuit, int suite,
+                                                              const uint32_t* seal, size_t seal_len,
+                                                              uint32_t* po2_out) {
+  return verify_entry_on(where, circuit, suite, seal, seal_len, false, nullptr, 0, nullptr, po2_out);
 }
 
 extern "C" const char* r0hip_poly_ext(const char* circuit, const uint32_t* h_mix, const uint32_t* h_global,

@@ -71,6 +71,17 @@ struct PendingOpening {
   size_t idx;
 };
 
+// What an opening backend returns per pending opening: `cur` as MerkleVerifier::check has it
+// when it reaches the comparison, and a status (0 computed; 2 a Poseidon2 path digest word is
+// >= p, where hash_pair throws). A backend hashes every opening of `pending` (rows and paths
+// point into [words, words + n_words)) and decides nothing: check_pending compares.
+struct OpeningResult {
+  Digest cur;
+  uint32_t status;
+};
+using OpeningBackend = void (*)(int suite, const uint32_t* words, size_t n_words,
+                                const std::vector<PendingOpening>& pending, OpeningResult* out);
+
 // read_iop.rs: a cursor over the seal plus the Fiat-Shamir RNG
 struct ReadIOP {
   const uint32_t* words;
@@ -79,6 +90,7 @@ struct ReadIOP {
   std::unique_ptr<Rng> rng;
   bool defer = false;  // Merkle openings go to `pending` instead of being hashed at once
   std::vector<PendingOpening> pending;
+  OpeningBackend backend = nullptr;  // null: check_pending hashes the openings on host threads
   ReadIOP(const uint32_t* w, size_t n, int s) : words(w), size(n), suite(s), rng(make_rng(s)) {}
   const uint32_t* read(size_t n) {
     if (n > size - pos) throw VerifyError("seal too short");
@@ -148,13 +160,36 @@ struct MerkleVerifier {
     const Digest& present = idx >= top_size ? top[idx - top_size] : rest[idx];
     if (!same(present, cur)) throw VerifyError("merkle path mismatch");
   }
+  // the digest check() compares with for row `idx`: the node where the path above the leaf ends
+  const Digest& present(size_t idx) const {
+    idx += rows;
+    while (idx >= 2 * top_size) idx >>= 1;
+    return idx >= top_size ? top[idx - top_size] : rest[idx];
+  }
+  size_t path_levels(size_t idx) const {
+    size_t levels = 0;
+    for (size_t i = idx + rows; i >= 2 * top_size; i >>= 1) levels++;
+    return levels;
+  }
 };
 
 // the deferred openings' hash paths on up to `threads` host threads; the first failure (in
-// opening order) is thrown
-inline void check_pending(ReadIOP& iop, unsigned threads) {
+// opening order) is thrown. With a backend the hashes come from it instead (one call for all
+// openings) and the comparison of check() runs here, in opening order, with check()'s messages.
+inline void check_pending(ReadIOP& iop, unsigned threads, OpeningBackend backend = nullptr) {
   const size_t n = iop.pending.size();
   if (n == 0) return;
+  if (backend) {
+    std::vector<OpeningResult> res(n);
+    backend(iop.suite, iop.words, iop.size, iop.pending, res.data());
+    for (size_t i = 0; i < n; i++) {
+      const PendingOpening& p = iop.pending[i];
+      if (res[i].status == 2) throw VerifyError("non-canonical Poseidon2 digest word in seal");
+      if (res[i].status != 0) throw std::runtime_error("r0hip: opening backend returned an unknown status");
+      if (!same(p.tree->present(p.idx), res[i].cur)) throw VerifyError("merkle path mismatch");
+    }
+    return;
+  }
   threads = unsigned(std::max<size_t>(1, std::min<size_t>(threads, n)));
   std::vector<std::string> err(threads);
   std::vector<size_t> err_at(threads, SIZE_MAX);
@@ -270,7 +305,7 @@ void fri_verify(ReadIOP& iop, size_t degree, Inner inner) {
     FpExt x = fe_from_fp(fp_pow(gen, pos));
     if (!fe_eq(poly_eval(final_poly.data(), degree, x), goal)) throw VerifyError("FRI final polynomial mismatch");
   }
-  check_pending(iop, verify_threads());  // while the rounds' verifiers are alive
+  check_pending(iop, verify_threads(), iop.backend);  // while the rounds' verifiers are alive
 }
 
 // verify_validity (mod.rs:292-474) then fri_verify and verify_complete (read_iop.rs:66-71),

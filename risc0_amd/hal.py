@@ -65,6 +65,9 @@ def _declare(L):
         "r0hip_prove_trace_segments": [C.c_int, C.c_uint32, C.c_void_p, sz, C.c_uint32, C.c_int],
         "r0hip_verify_seal": [C.c_char_p, C.c_int, u32p, sz, u32p, sz, u32p, C.POINTER(C.c_uint32)],
         "r0hip_testing_verify_seal_structure": [C.c_char_p, C.c_int, u32p, sz, C.POINTER(C.c_uint32)],
+        "r0hip_verify_seal_on": [C.c_int, C.c_char_p, C.c_int, u32p, sz, u32p, sz, u32p, C.POINTER(C.c_uint32)],
+        "r0hip_testing_verify_seal_structure_on": [C.c_int, C.c_char_p, C.c_int, u32p, sz, C.POINTER(C.c_uint32)],
+        "r0hip_merkle_open_digests": [C.c_int, u32p, sz, vp, sz, u32p, u32p],
         "r0hip_poly_ext": [C.c_char_p, u32p, u32p, u32p, u32p, u32p],
         "r0hip_synchronize": [],
         "r0hip_set_deferred": [C.c_int, C.POINTER(C.c_int)],
@@ -1013,11 +1016,27 @@ class _HostBlock:
             self.ptr = None
 
 
+VERIFY_RECEIPTS_DEVICE = 2  # R0HIP_VERIFY_RECEIPTS_DEVICE
+
+
+def _verify_mode(verify):
+    """The pipelines' `verify` argument: "device" or 2 asks for the receipt check with the seal's
+    Merkle openings hashed on the device; anything else is its truth value (True passes 1)."""
+    if isinstance(verify, str):
+        if verify not in ("host", "device"):
+            raise ValueError(f"verify = {verify!r}: expected a bool, 2, \"host\" or \"device\"")
+        return VERIFY_RECEIPTS_DEVICE if verify == "device" else 1
+    if verify is not True and verify is not False and verify == VERIFY_RECEIPTS_DEVICE:
+        return VERIFY_RECEIPTS_DEVICE
+    return int(bool(verify))
+
+
 def prove_trace_segments(hal, po2, traces, in_flight=2, seal_cap=1 << 22, verify=True, per_job=False):
     """The GPU worker unit (r0hip_prove_trace_segments): each TraceJob is one rv32im prove_core
     from its preflight trace; an uploader copies the traces into in_flight + 1 device trace sets
     while in_flight provers run, and (verify) every seal is checked by the native verifier, the
-    validity equation included, on a host thread beside the proofs. Returns [(seal, mix)] in job
+    validity equation included, on a host thread beside the proofs (verify="device" or 2: with the
+    seal's Merkle openings hashed on the device, _verify_mode). Returns [(seal, mix)] in job
     order and raises on any failed job; per_job=True returns [(seal, mix, error or None,
     verify_ms, prove_ms)] instead, without raising for a job's own failure (prove_ms: from a
     prover taking the job to its seal in host memory)."""
@@ -1032,7 +1051,7 @@ def prove_trace_segments(hal, po2, traces, in_flight=2, seal_cap=1 << 22, verify
         mixes.append(np.zeros(36, dtype=np.uint32))
         j.h_seal, j.seal_cap, j.h_mix_out = seals[-1].ctypes.data, seal_cap, mixes[-1].ctypes.data
     err = lib().r0hip_prove_trace_segments(hal.suite, po2, C.cast(jobs, C.c_void_p), len(traces), in_flight,
-                                           int(bool(verify)))
+                                           _verify_mode(verify))
     errors = []
     for j in jobs:
         errors.append(C.cast(j.error, C.c_char_p).value.decode() if j.error else None)
@@ -1119,7 +1138,7 @@ class Worker:
     worker, which first runs everything submitted to completion."""
 
     def __init__(self, hal, max_po2, in_flight=2, verify=True, noise_key=None, seal_cap=1 << 22):
-        self.hal, self.verify, self.seal_cap = hal, bool(verify), seal_cap
+        self.hal, self.verify, self.seal_cap = hal, _verify_mode(verify), seal_cap  # 0, 1 or 2 ("device")
         self._pending = {}  # address of the job struct -> (struct, seal, mix, inputs)
         self.outputs = {}  # ticket of a returned kind-4 job -> Preflight.output, until output() reads it
         k, kp = _key_words(noise_key)
@@ -1330,8 +1349,35 @@ def prove_segments(hal, circuit, po2, witnesses, version=None, in_flight=2, seal
     return [(seal[: j.seal_len].copy(), mix) for j, seal, mix in zip(jobs, seals, mixes)]
 
 
-def verify_seal(circuit, suite, seal, check_validity=True, code_roots=None, return_code_root=False):
-    """r0hip_verify_seal: the native seal verifier (host-only, no GPU); returns the
+class Opening(C.Structure):
+    """struct r0hip_opening (include/r0hip.h): one Merkle opening over a word buffer"""
+    _fields_ = [("row_off", C.c_uint64), ("path_off", C.c_uint64), ("index", C.c_uint64), ("cols", C.c_uint32),
+                ("levels", C.c_uint32)]
+
+
+def merkle_open_digests(suite, words, openings):
+    """r0hip_merkle_open_digests: the device step of the receipt check by itself. `openings` is a
+    list of (row_off, path_off, index, cols, levels) over the u32 array `words`; returns
+    (digests [n, 8], status [n]): per opening the row hash folded up its path, and 0 or 2 (a
+    Poseidon2 path digest word >= p). Suites Poseidon2 and SHA-256."""
+    words = np.ascontiguousarray(words, dtype=np.uint32)
+    sid = SUITES[suite] if isinstance(suite, str) else suite
+    n = len(openings)
+    table = (Opening * max(n, 1))()
+    for t, o in zip(table, openings):
+        t.row_off, t.path_off, t.index, t.cols, t.levels = (int(v) for v in o)
+    digests, status = np.zeros((n, 8), np.uint32), np.zeros(n, np.uint32)
+    check(lib().r0hip_merkle_open_digests(sid, words.ctypes.data_as(u32p), words.size, C.cast(table, C.c_void_p), n,
+                                          digests.ctypes.data_as(u32p), status.ctypes.data_as(u32p)))
+    return digests, status
+
+
+VERIFY_WHERE = {"host": 0, "device": 1}  # R0HIP_VERIFY_HOST, R0HIP_VERIFY_DEVICE
+
+
+def verify_seal(circuit, suite, seal, check_validity=True, code_roots=None, return_code_root=False, where="host"):
+    """r0hip_verify_seal: the native seal verifier (host-only, no GPU; where="device": the same
+    check through r0hip_verify_seal_on with the seal's Merkle openings hashed on the GPU); returns the
     segment po2 (and the code root, 8 words, with return_code_root), raises R0HipError
     naming the failed check. code_roots: allowed code/control roots (check_code,
     zkp/src/verify/mod.rs:531). check_validity=False calls the test-only
@@ -1340,14 +1386,24 @@ def verify_seal(circuit, suite, seal, check_validity=True, code_roots=None, retu
     seal = np.ascontiguousarray(seal, dtype=np.uint32)
     po2 = C.c_uint32(0)
     sid = SUITES[suite] if isinstance(suite, str) else suite
+    on = VERIFY_WHERE[where] if isinstance(where, str) else int(where)
     if not check_validity:
         assert code_roots is None and not return_code_root, "the structure check binds no code root"
+        if on != 0:
+            check(lib().r0hip_testing_verify_seal_structure_on(on, circuit.encode(), sid, seal.ctypes.data_as(u32p),
+                                                               seal.size, C.byref(po2)))
+            return po2.value
         check(lib().r0hip_testing_verify_seal_structure(circuit.encode(), sid, seal.ctypes.data_as(u32p), seal.size,
                                                         C.byref(po2)))
         return po2.value
     roots = np.ascontiguousarray(np.zeros(0, np.uint32) if code_roots is None else code_roots, dtype=np.uint32)
     assert roots.size % 8 == 0
     root_out = np.zeros(8, np.uint32)
+    if on != 0:
+        check(lib().r0hip_verify_seal_on(on, circuit.encode(), sid, seal.ctypes.data_as(u32p), seal.size,
+                                         roots.ctypes.data_as(u32p), roots.size // 8, root_out.ctypes.data_as(u32p),
+                                         C.byref(po2)))
+        return (po2.value, root_out) if return_code_root else po2.value
     check(lib().r0hip_verify_seal(circuit.encode(), sid, seal.ctypes.data_as(u32p), seal.size,
                                   roots.ctypes.data_as(u32p), roots.size // 8, root_out.ctypes.data_as(u32p),
                                   C.byref(po2)))
