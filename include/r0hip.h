@@ -93,6 +93,24 @@ const char* r0hip_set_deferred(int on, int* was);
  * While r0hip_set_kernel_timing is on the thread behaves as n = 1. */
 /* [drains] */
 const char* r0hip_set_proof_streams(uint32_t n, uint32_t* was);
+/* Constraint check of the witness inside the provers (thread-local, like the two modes above;
+ * off on every new thread, and the library's own pipeline threads never turn it on; a worker's
+ * prover threads follow r0hip_worker_set_witness_check). on != 0: every proof of the calling
+ * thread that goes through the segment prover (r0hip_prove_segment, _accum, _trace, _trace_backs,
+ * _trace_resident and the four r0hip_prove_recursion* calls) evaluates the circuit's constraint
+ * polynomial on the 2^po2 rows of its three groups once they are in their final form (after the
+ * accumulation, before the accum group is committed), as r0hip_constraint_rows does, with a
+ * poly_mix from getrandom(2). Nothing is drawn from the transcript: a witness that satisfies the
+ * constraints gives the seal of the mode off, word for word. One that does not fails the call
+ * with exactly
+ *   constraint check failed: K of N rows, first at cycle R (term T)
+ * (K bad rows of N = 2^po2, R the first, T the id in <circuit>.poly.ir of the first violated term,
+ * r0hip_constraint_term) and writes no seal, instead of paying for a proof that the receipt check
+ * then rejects. r0hip_last_profile carries a check_witness mark while the mode is on. A
+ * diagnostic for bring-up, not part of soundness. *was (may be NULL) receives
+ * the previous mode. */
+/* [host-only] */
+const char* r0hip_set_witness_check(int on, int* was);
 /* The calling thread's entry-point calls so far, no device work: out[0] = [queues] and [drains]
  * calls made, out[1] = those that drained the stream before returning, out[2] = those that
  * returned with their work only queued. */
@@ -828,6 +846,13 @@ const char* r0hip_worker_submit(r0hip_worker* w, r0hip_worker_job* job);
 const char* r0hip_worker_wait(r0hip_worker* w, r0hip_worker_job** done, int64_t timeout_ms);
 /* [drains] */
 const char* r0hip_worker_destroy(r0hip_worker* w);
+/* r0hip_set_witness_check for the worker's jobs: the switch applies to the jobs submitted after
+ * the call and is recorded at r0hip_worker_submit (the job structs keep their layout); the prover
+ * thread that takes a job sets its own mode to the job's. A job whose witness violates a
+ * constraint gets "constraint check failed: ..." in its own error, verified = 0 and no seal; the
+ * other jobs are untouched, and a passing job's seal is that of the switch off. */
+/* [host-only] */
+const char* r0hip_worker_set_witness_check(r0hip_worker* w, int on);
 
 /* ---- seal verification (risc0/zkp/src/verify/mod.rs:500-560 `verify`, with merkle.rs:79-186,
  * fri.rs:36-155, read_iop.rs:20-84; rv32im seals lead with the version word 2,
@@ -904,6 +929,48 @@ const char* r0hip_merkle_open_digests(int suite, const uint32_t* h_words, size_t
 /* [host-only] */
 const char* r0hip_poly_ext(const char* circuit, const uint32_t* h_mix, const uint32_t* h_global,
                            const uint32_t* h_eval_u, const uint32_t* h_poly_mix, uint32_t* h_out);
+
+/* ---- constraint check on the trace rows (a diagnostic, opt-in) ----
+ * The circuit's constraint polynomial vanishes on every row of a valid trace, the ZK rows
+ * included. r0hip_constraint_rows evaluates it (poly_fp of the reference, with poly_mix given) on
+ * the 2^po2 rows of the witness groups as they are: d_code, d_data and d_accum are the device
+ * matrices r0hip_prove_segment takes (column-major, 2^po2 rows; the groups in their final form,
+ * zeroized and accumulated), d_mix and d_global the device arrays r0hip_eval_check takes. A tap is
+ * read at (row - back) mod 2^po2, so a `back` at or above 2^po2 wraps. h_poly_mix: four Montgomery
+ * words (one FpExt); NULL draws them with getrandom(2). d_out (may be NULL): the value of every
+ * row, one FpExt (4 words, AoS) per row, 2^po2 * 4 words, bit for bit the reference's poly_fp on
+ * that row's taps. The report: bad_rows = how many rows are nonzero, first_row the smallest of
+ * them, rows[0 .. n_rows) the first n_rows = min(bad_rows, 16) in ascending order (0xFFFFFFFF
+ * beyond, and first_row = 0xFFFFFFFF when there is none), first_term = r0hip_constraint_term on
+ * first_row, whose taps the call gathers to the host (-1 when no row is bad). A violated witness
+ * is a successful call with bad_rows > 0, not an error. po2 is 2..24. Refused on the host, naming
+ * the argument, before any device call: a NULL pointer (all but h_poly_mix and d_out), an unknown
+ * circuit, po2 out of range.
+ * Not part of soundness: a violated row gives zero for a random poly_mix with probability at most
+ * (number of terms) / p^4, and the check says nothing about a prover that goes on to commit
+ * other values. It answers "is the witness wrong, or the polynomial side?" in a quarter of
+ * eval_check's points, before the proof is paid for.
+ * r0hip_constraint_term: the host half alone; needs no GPU and no r0hip_init. h_taps: one row's
+ * tap values, one Montgomery word per tap in tap order (the order of r0hip_poly_ext's h_eval_u);
+ * h_mix, h_global, h_poly_mix as r0hip_poly_ext takes them. *term = the value id, in the
+ * committed risc0_amd/circuits/<circuit>.poly.ir, of the first violated term: the accumulate
+ * chain that ends at the `r` record is walked in chain order for the first `a`/`b` record whose
+ * added amount is nonzero; for a `b` (a guarded block) the walk repeats inside its inner chain
+ * and the innermost id is returned. -1 when the row satisfies every constraint. */
+typedef struct r0hip_constraint_report {
+  uint64_t bad_rows;   /* rows whose constraint value is nonzero */
+  uint32_t first_row;  /* the smallest of them, 0xFFFFFFFF if none */
+  int32_t first_term;  /* r0hip_constraint_term on first_row, -1 if none */
+  uint32_t n_rows;     /* entries of rows[] in use: min(bad_rows, 16) */
+  uint32_t rows[16];   /* the first bad rows, ascending */
+} r0hip_constraint_report;
+/* [drains] */
+const char* r0hip_constraint_rows(const char* circuit, uint32_t po2, const uint32_t* d_code, const uint32_t* d_data,
+                                  const uint32_t* d_accum, const uint32_t* d_mix, const uint32_t* d_global,
+                                  const uint32_t* h_poly_mix, uint32_t* d_out, r0hip_constraint_report* report);
+/* [host-only] */
+const char* r0hip_constraint_term(const char* circuit, const uint32_t* h_taps, const uint32_t* h_mix,
+                                  const uint32_t* h_global, const uint32_t* h_poly_mix, int32_t* term);
 
 /* kernel-level timing with HIP events on the library stream: enable, run, then read
  * "name=total_ms:calls:alg_bytes;..." (alg_bytes = algorithmic HBM bytes) */

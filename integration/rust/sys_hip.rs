@@ -27,6 +27,16 @@ pub const R0HIP_SHA256: c_int = 1;
 pub const R0HIP_POSEIDON254: c_int = 2;
 
 /// One Back::BigInt record of the rv32im preflight trace (struct r0hip_bigint_back).
+/// struct r0hip_constraint_report: what r0hip_constraint_rows found on the trace rows.
+#[repr(C)]
+pub struct R0HipConstraintReport {
+    pub bad_rows: u64,
+    pub first_row: u32,
+    pub first_term: i32,
+    pub n_rows: u32,
+    pub rows: [u32; 16],
+}
+
 #[repr(C)]
 pub struct R0HipBigIntBack {
     pub row: u32,
@@ -244,6 +254,9 @@ unsafe extern "C" {
     pub fn r0hip_call_stats(out: *mut u64) -> *const c_char;
     // streams one proof of the calling thread may use (1..3; for a worker proving one task at a time)
     pub fn r0hip_set_proof_streams(n: u32, was: *mut u32) -> *const c_char;
+    // the calling thread's witness check: the provers evaluate the constraint polynomial on the
+    // trace rows before the accum commit and fail with "constraint check failed: ..." (opt-in)
+    pub fn r0hip_set_witness_check(on: c_int, was: *mut c_int) -> *const c_char;
     pub fn r0hip_free_error(err: *const c_char);
     // a device-to-host copy beside later calls (the HAL's node-heap mirrors, hal_hip.rs)
     pub fn r0hip_memcpy_d2h_start(h_dst: *mut c_void, d_src: *const c_void, bytes: usize,
@@ -664,6 +677,8 @@ unsafe extern "C" {
     pub fn r0hip_worker_submit(w: *mut R0HipWorker, job: *mut R0HipWorkerJob) -> *const c_char;
     pub fn r0hip_worker_wait(w: *mut R0HipWorker, done: *mut *mut R0HipWorkerJob, timeout_ms: i64) -> *const c_char;
     pub fn r0hip_worker_destroy(w: *mut R0HipWorker) -> *const c_char;
+    // the witness check for the jobs submitted from now on (recorded at submit)
+    pub fn r0hip_worker_set_witness_check(w: *mut R0HipWorker, on: c_int) -> *const c_char;
 
     // ---- verification (host-only) ----
     pub fn r0hip_verify_seal(
@@ -719,6 +734,29 @@ unsafe extern "C" {
         h_eval_u: *const u32,
         h_poly_mix: *const u32,
         h_out: *mut u32,
+    ) -> *const c_char;
+    // the constraint polynomial on the 2^po2 trace rows of the witness groups (a diagnostic):
+    // d_out (may be null) gets one FpExt per row, the report names the rows that are nonzero
+    pub fn r0hip_constraint_rows(
+        circuit: *const c_char,
+        po2: u32,
+        d_code: *const u32,
+        d_data: *const u32,
+        d_accum: *const u32,
+        d_mix: *const u32,
+        d_global: *const u32,
+        h_poly_mix: *const u32,
+        d_out: *mut u32,
+        report: *mut R0HipConstraintReport,
+    ) -> *const c_char;
+    // host-only: the id in <circuit>.poly.ir of the first term one row's taps violate (-1: none)
+    pub fn r0hip_constraint_term(
+        circuit: *const c_char,
+        h_taps: *const u32,
+        h_mix: *const u32,
+        h_global: *const u32,
+        h_poly_mix: *const u32,
+        term: *mut i32,
     ) -> *const c_char;
 
     // ---- diagnostics (scope! spans and the MemoryTracker) ----

@@ -44,6 +44,7 @@ GroupWork commit_group_side(int k, int suite, const uint32_t* witness, size_t co
 std::vector<uint32_t> commit_group_keep(hipStream_t s, int suite, uint32_t* coeffs, uint32_t* evaluated, uint32_t* nodes,
                                         const uint32_t* witness, size_t cols, size_t po2);
 std::string last_profile();
+FpExt constraint_rows_poly_mix(const uint32_t* h_poly_mix);  // the caller's four words, or the OS's
 }  // namespace r0
 
 using namespace r0;
@@ -167,6 +168,12 @@ const char* r0hip_set_proof_streams(uint32_t n, uint32_t* was) {
   return wrap([&] {
     if (was) *was = proof_streams();
     set_proof_streams(n);
+  });
+}
+const char* r0hip_set_witness_check(int on, int* was) {
+  return wrap_nosync([&] {
+    const bool w = set_witness_check_mode(on != 0);
+    if (was) *was = w ? 1 : 0;
   });
 }
 const char* r0hip_call_stats(uint64_t* out) {
@@ -1208,6 +1215,28 @@ const char* r0hip_eval_check(const char* circuit, uint32_t* d_check, const uint3
     for (int g = 0; g < 3; g++) R0_REQUIRE(d_groups[g], "eval_check: null register group");
     stage_reset();
     run_eval_check(*c, d_check, d_groups, d_mix, d_global, fe(h_poly_mix), po2);
+  });
+}
+
+const char* r0hip_constraint_rows(const char* circuit, uint32_t po2, const uint32_t* d_code, const uint32_t* d_data,
+                                  const uint32_t* d_accum, const uint32_t* d_mix, const uint32_t* d_global,
+                                  const uint32_t* h_poly_mix, uint32_t* d_out, r0hip_constraint_report* report) {
+  return wrap([&] {
+    // every refusal on the host, before any device call
+    const std::string who = "r0hip_constraint_rows: ";
+    const CircuitDef* c = find_circuit(circuit ? circuit : "");
+    R0_REQUIRE(c, who + "unknown circuit " + (circuit ? circuit : "(null)"));
+    R0_REQUIRE(po2 >= 2 && po2 <= 24, who + "po2 " + std::to_string(po2) + " out of range (2..24)");
+    R0_REQUIRE(d_code, who + "d_code is NULL");
+    R0_REQUIRE(d_data, who + "d_data is NULL");
+    R0_REQUIRE(d_accum, who + "d_accum is NULL");
+    R0_REQUIRE(d_mix, who + "d_mix is NULL");
+    R0_REQUIRE(d_global, who + "d_global is NULL");
+    R0_REQUIRE(report, who + "report is NULL");
+    const FpExt poly_mix = constraint_rows_poly_mix(h_poly_mix);
+    stage_reset();
+    const uint32_t* groups[3] = {d_accum, d_code, d_data};
+    constraint_rows_run(*c, po2, groups, d_mix, d_global, nullptr, nullptr, poly_mix, d_out, report);
   });
 }
 

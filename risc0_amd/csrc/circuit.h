@@ -31,6 +31,9 @@ struct CircuitDef {
   size_t n_eval_args;
   void (*eval_check)(hipStream_t, const EvalCheckArgs&);
   void (*info)(EvalCheckInfo*);
+  // the same program on the trace rows (evalcheck.h: the constraint-rows family)
+  void (*constraint_rows)(hipStream_t, const EvalCheckArgs&);
+  void (*rows_info)(EvalCheckInfo*);
   // the constraint program for the host poly_ext (verify.cpp): n_ir records of
   // {op, dst, a, b, c, d}, op index into "celg+-*abr", dst dense 0..n_ir-1
   const uint32_t* ir;

@@ -522,6 +522,44 @@ __global__ void gather_words_kernel(uint32_t* dst, const uint32_t* const* bases,
   if (i < n) dst[i] = bases[base_id[i]][offsets[i]];
 }
 
+
+// The report of a constraint-rows check (rows_report): over n FpExt values (AoS), the number of
+// nonzero ones, the smallest nonzero index and the 16 smallest nonzero indices in ascending
+// order. out: words 0..1 the count (64 bits), word 2 the smallest index, words 3..18 the list;
+// the caller sets the count to 0 and words 2..18 to 0xFFFFFFFF ("none") first.
+// One pass, plain atomics on those 19 words. The count and the minimum take one atomic per wave
+// that holds a nonzero row. The list is a cascade of atomicMin: an index is offered to slot 0,
+// whichever of the two is larger moves on to slot 1, and so on. A slot only ever decreases and
+// no index is lost (each is in a slot or carried by a lane), so slot k ends as the (k+1)-th
+// smallest whatever the order of arrival: the result does not depend on the launch shape. An
+// index at or above the current slot 15 has 16 smaller ones ahead of it and is skipped, so a
+// witness with every row wrong costs about one read of that word per row, not 16 atomics.
+__global__ void rows_report_kernel(const uint4* vals, uint64_t n, uint32_t* out) {
+  const uint64_t stride = uint64_t(gridDim.x) * kThreads;
+  for (uint64_t b = uint64_t(blockIdx.x) * kThreads; b < n; b += stride) {
+    const uint64_t i = b + threadIdx.x;
+    bool bad = false;
+    if (i < n) {
+      const uint4 v = vals[i];
+      bad = (v.x | v.y | v.z | v.w) != 0;
+    }
+    const uint64_t m = __ballot(bad);  // b is the same in every lane: whole waves reach this
+    const uint32_t lane = threadIdx.x & 63u;
+    if (m && lane == uint32_t(__ffsll(static_cast<long long>(m)) - 1)) {  // the wave's lowest bad row
+      atomicAdd(reinterpret_cast<unsigned long long*>(out), static_cast<unsigned long long>(__popcll(m)));
+      atomicMin(out + 2, uint32_t(i));
+    }
+    uint32_t v = uint32_t(i);
+    if (bad && v < __atomic_load_n(out + 3 + 15, __ATOMIC_RELAXED)) {
+      for (int k = 0; k < 16; k++) {
+        const uint32_t old = atomicMin(out + 3 + k, v);
+        if (old == 0xFFFFFFFFu) break;  // the slot was empty: nothing is carried on
+        if (old > v) v = old;           // the displaced index moves down the list
+      }
+    }
+  }
+}
+
 }  // namespace
 
 void eltwise_add(hipStream_t s, uint32_t* out, const uint32_t* a, const uint32_t* b, size_t n) {
@@ -743,6 +781,16 @@ void combos_sub(hipStream_t s, uint32_t* combos, const uint32_t* deltas, size_t 
   if (!rows || !width) return;
   hipLaunchKernelGGL(combos_sub_kernel, dim3(div_up(rows * width, kThreads)), dim3(kThreads), 0, s, combos, deltas,
                      uint32_t(rows), uint32_t(width), uint64_t(cycles));
+  HIP_OK(hipGetLastError());
+}
+
+void rows_report(hipStream_t s, const uint32_t* vals, size_t n, uint32_t* out) {
+  static_assert(kThreads % 64 == 0, "rows_report_kernel ballots whole waves");
+  HIP_OK(hipMemsetD32Async(out, 0u, 2, s));
+  HIP_OK(hipMemsetD32Async(out + 2, 0xFFFFFFFFu, 17, s));
+  if (!n) return;
+  hipLaunchKernelGGL(rows_report_kernel, dim3(grid_stride(n, kThreads)), dim3(kThreads), 0, s,
+                     reinterpret_cast<const uint4*>(vals), uint64_t(n), out);
   HIP_OK(hipGetLastError());
 }
 

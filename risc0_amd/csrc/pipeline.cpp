@@ -23,6 +23,7 @@
 #include <deque>
 #include <functional>
 #include <mutex>
+#include <set>
 #include <stdexcept>
 #include <string>
 #include <thread>
@@ -440,6 +441,7 @@ struct WorkerSet : TraceSet {
   PinnedWords pf_wom, pf_iops;  // kind-4 jobs: the preflight's WOM and IOP values
   std::vector<uint32_t> pf_out;
   r0hip_worker_job* wjob = nullptr;
+  bool witness_check = false;  // wjob's r0hip_worker_set_witness_check mode, as recorded at its submit
   size_t cap_inj = 0, cap_txn = 0, cap_big = 0;  // entries, records, bytes
   // kind-2 jobs: the Back records and their payload words (allocated at the set's first one),
   // the counts of the uploader's check and the BigInt records it derived for the accumulation
@@ -472,6 +474,11 @@ struct WorkerImpl {
   std::deque<r0hip_worker_job*> finished;
   std::deque<std::pair<r0hip_worker_job*, BacksInfo>> fifo;  // with the submit check's counts (kind 2)
   uint64_t next_ticket = 0;
+  // r0hip_worker_set_witness_check: the switch, and the queued jobs submitted while it was on (a
+  // job struct has no room for the mode and keeps its layout); the uploader moves a job's entry
+  // to its set
+  bool witness_check = false;
+  std::set<const r0hip_worker_job*> checked_jobs;
   size_t outstanding = 0;
   bool stopping = false;
   std::mutex vmu;
@@ -543,6 +550,7 @@ struct WorkerImpl {
     for (;;) {
       r0hip_worker_job* j;
       BacksInfo info;
+      bool job_check = false;
       {
         std::unique_lock<std::mutex> lk(mu);
         cv_in.wait(lk, [&] { return !fifo.empty() || stopping; });
@@ -550,6 +558,7 @@ struct WorkerImpl {
         j = fifo.front().first;
         info = fifo.front().second;
         fifo.pop_front();
+        job_check = checked_jobs.erase(j) != 0;
       }
       const long s = free_q.get();
       WorkerSet& b = sets[s];
@@ -564,6 +573,7 @@ struct WorkerImpl {
       {
         std::lock_guard<std::mutex> lk(b.mu);
         b.wjob = j;
+        b.witness_check = job_check;
         b.landed = false;
       }
       try {
@@ -635,6 +645,7 @@ struct WorkerImpl {
       {
         std::lock_guard<std::mutex> lk(b.mu);
         j = b.wjob;
+        set_witness_check_mode(b.witness_check);  // this prover thread's mode, for this job
       }
       const auto t0 = std::chrono::steady_clock::now();
       std::vector<uint32_t> seal;
@@ -1099,8 +1110,17 @@ extern "C" const char* r0hip_worker_submit(r0hip_worker* w, r0hip_worker_job* jo
       job->ticket = m.next_ticket++;
       m.outstanding++;
       m.fifo.emplace_back(job, info);
+      if (m.witness_check) m.checked_jobs.insert(job);
     }
     m.cv_in.notify_one();
+  });
+}
+
+extern "C" const char* r0hip_worker_set_witness_check(r0hip_worker* w, int on) {
+  return guarded([&] {
+    R0_REQUIRE(w, "r0hip_worker_set_witness_check: w is NULL");
+    std::lock_guard<std::mutex> lk(w->impl.mu);
+    w->impl.witness_check = on != 0;
   });
 }
 

@@ -18,6 +18,7 @@
 #include <string>
 #include <vector>
 
+#include "../../include/r0hip.h"
 #include "circuit.h"
 #include "devmem.h"
 #include "runtime.h"
@@ -288,14 +289,16 @@ GroupWork commit_group_side(int k, int suite, const uint32_t* witness, size_t co
   return w;
 }
 
-// eval_check for one circuit (rv32im/src/prove/hal/cpu.rs:145-207 semantics)
-void run_eval_check(const CircuitDef& c, uint32_t* check, const uint32_t* const* groups, const uint32_t* mix,
-                    const uint32_t* global, FpExt poly_mix, size_t po2, const uint32_t* h_mix,
-                    const uint32_t* h_global) {
-  hipStream_t s = stream();
-  EvalCheckInfo info;
-  c.info(&info);
-  size_t steps = size_t(1) << po2, domain = steps * INV_RATE;
+namespace {
+// What the generated kernels of either family (evalcheck.h) read besides the result buffer, for
+// groups of `domain` rows: the poly_mix powers and folded products with their NBETA multiples,
+// the argument and column base pointers, the lane-independent values (from host copies of mix and
+// global, read back into hm/hg when the caller has none and the kernels need them) and the
+// scratch of the materialised values. `args` backs e.args and outlives the launch.
+void ec_tables(const CircuitDef& c, const EvalCheckInfo& info, const uint32_t* const* groups, const uint32_t* mix,
+               const uint32_t* global, FpExt poly_mix, size_t domain, const uint32_t*& h_mix, const uint32_t*& h_global,
+               std::vector<uint32_t>& hm, std::vector<uint32_t>& hg, std::vector<const uint32_t*>& args,
+               EvalCheckArgs& e) {
   std::vector<FpExt> pm = map_pow(poly_mix, c.poly_mix_powers, c.n_poly_mix);
   R0_REQUIRE(pm.size() >= size_t(info.npm), "poly_mix table shorter than the kernels expect");
   pm.resize(info.npm);
@@ -305,20 +308,11 @@ void run_eval_check(const CircuitDef& c, uint32_t* check, const uint32_t* const*
     for (int q = 0; q < n; q++) prod = fe_mul(prod, pm[info.combos[k++]]);
     pm.push_back(prod);
   }
-  // inv((3 * w_D^c)^N - 1) depends only on c mod 4 (w_D^(cN) = w_4^c)
-  std::vector<uint32_t> vinv(4);
-  uint32_t w = fp_encode(kRouFwd[po2 + 2]);
-  for (uint32_t q = 0; q < 4; q++) {
-    uint32_t x = fp_pow(w, q);
-    uint32_t y = fp_pow(fp_mul(fp_encode(3), x), steps);
-    vinv[q] = fp_inv(fp_sub(y, kOne));
-  }
-  std::vector<const uint32_t*> args(c.n_eval_args);
+  args.resize(c.n_eval_args);
   for (size_t i = 0; i < c.n_eval_args; i++) {
     int a = c.eval_args[i];
     args[i] = a >= 0 ? groups[a] : (a == -1 ? mix : global);
   }
-  EvalCheckArgs e;
   e.args = args.data();
   e.nargs = args.size();
   // one base pointer per column the generated program reads (saddr-form tap loads)
@@ -329,12 +323,10 @@ void run_eval_check(const CircuitDef& c, uint32_t* check, const uint32_t* const*
   std::vector<FpExt> pmn(pm.size());
   for (size_t i = 0; i < pm.size(); i++) pmn[i] = fe_mul_fp(pm[i], kNBeta);
   e.poly_mix_nb = upload(pmn, kSlotEcPolyMixNb);
-  e.vinv = upload(vinv, kSlotEcVinv);
   // the lane-independent values (functions of mix, global and poly_mix only), from host
   // copies of mix and global (read back here when the caller has none)
   std::vector<uint32_t> uv(4 * size_t(info.n_uniform > 0 ? info.n_uniform : 1), 0);
   if (info.n_uniform > 0) {
-    std::vector<uint32_t> hm, hg;
     if (!h_mix && c.mix_size) {
       hm.resize(c.mix_size);
       d2h(hm.data(), mix, c.mix_size * 4);
@@ -353,11 +345,35 @@ void run_eval_check(const CircuitDef& c, uint32_t* check, const uint32_t* const*
     info.uniform(hargs.data(), reinterpret_cast<const uint32_t*>(pm.data()), uv.data());
   }
   e.uniform = upload(uv, kSlotEcUniform);
-  e.acc = static_cast<uint32_t*>(scratch(domain * 16, kSlotEcAcc));
   e.mat_fp = static_cast<uint32_t*>(scratch(size_t(info.mat_fp) * domain * 4 + 16, kSlotEcMatFp));
   e.mat_ext = static_cast<uint32_t*>(scratch(size_t(info.mat_ext) * domain * 16 + 16, kSlotEcMatExt));
-  e.check = check;
   e.domain = uint32_t(domain);
+}
+}  // namespace
+
+// eval_check for one circuit (rv32im/src/prove/hal/cpu.rs:145-207 semantics)
+void run_eval_check(const CircuitDef& c, uint32_t* check, const uint32_t* const* groups, const uint32_t* mix,
+                    const uint32_t* global, FpExt poly_mix, size_t po2, const uint32_t* h_mix,
+                    const uint32_t* h_global) {
+  hipStream_t s = stream();
+  EvalCheckInfo info;
+  c.info(&info);
+  size_t steps = size_t(1) << po2, domain = steps * INV_RATE;
+  std::vector<uint32_t> hm, hg;
+  std::vector<const uint32_t*> args;
+  EvalCheckArgs e;
+  ec_tables(c, info, groups, mix, global, poly_mix, domain, h_mix, h_global, hm, hg, args, e);
+  // inv((3 * w_D^c)^N - 1) depends only on c mod 4 (w_D^(cN) = w_4^c)
+  std::vector<uint32_t> vinv(4);
+  uint32_t w = fp_encode(kRouFwd[po2 + 2]);
+  for (uint32_t q = 0; q < 4; q++) {
+    uint32_t x = fp_pow(w, q);
+    uint32_t y = fp_pow(fp_mul(fp_encode(3), x), steps);
+    vinv[q] = fp_inv(fp_sub(y, kOne));
+  }
+  e.vinv = upload(vinv, kSlotEcVinv);
+  e.acc = static_cast<uint32_t*>(scratch(domain * 16, kSlotEcAcc));
+  e.check = check;
   {
     static const uint32_t tile_env = [] {
       const char* t = getenv("R0_EC_TILE");
@@ -374,6 +390,91 @@ void run_eval_check(const CircuitDef& c, uint32_t* check, const uint32_t* const*
   Span span("eval_check");
   KScope ks("eval_check", bytes, double(domain) * info.modmuls_per_point);
   c.eval_check(s, e);
+}
+
+// The constraint polynomial on the trace rows (runtime.h): eval_check's tables for N rows in
+// place of the 4N domain, the groups as they are, no vanishing-polynomial factor. Then the report
+// kernel, its 19 words back, and for a bad witness the first bad row's taps and its term.
+void constraint_rows_run(const CircuitDef& c, size_t po2, const uint32_t* const* groups, const uint32_t* mix,
+                         const uint32_t* global, const uint32_t* h_mix, const uint32_t* h_global, FpExt poly_mix,
+                         uint32_t* vals, r0hip_constraint_report* report) {
+  hipStream_t s = stream();
+  EvalCheckInfo info;
+  c.rows_info(&info);
+  const size_t rows = size_t(1) << po2;
+  std::vector<uint32_t> hm, hg;
+  std::vector<const uint32_t*> args;
+  EvalCheckArgs e;
+  ec_tables(c, info, groups, mix, global, poly_mix, rows, h_mix, h_global, hm, hg, args, e);
+  e.acc = vals ? vals : static_cast<uint32_t*>(scratch(rows * 16, kSlotEcAcc));
+  e.check = nullptr;
+  e.vinv = nullptr;
+  e.wide = 0;
+  auto* d_rep = static_cast<uint32_t*>(scratch(19 * 4, kSlotRowsReport));
+  {
+    double bytes = 16.0 * rows;
+    for (int g = 0; g < 3; g++) bytes += 4.0 * rows * c.group_sizes[g];
+    Span span("constraint_rows");
+    KScope ks("constraint_rows", bytes, double(rows) * info.modmuls_per_point);
+    c.constraint_rows(s, e);
+    rows_report(s, e.acc, rows, d_rep);
+  }
+  uint32_t rep[19];
+  d2h(rep, d_rep, sizeof rep);
+  *report = r0hip_constraint_report{};
+  report->bad_rows = uint64_t(rep[0]) | (uint64_t(rep[1]) << 32);
+  report->first_row = rep[2];
+  report->first_term = -1;
+  for (int k = 0; k < 16; k++) {
+    report->rows[k] = rep[3 + k];
+    if (rep[3 + k] != 0xFFFFFFFFu) report->n_rows = uint32_t(k + 1);
+  }
+  if (!report->bad_rows) return;
+  // the first bad row's taps, in tap order, and the term they violate
+  std::vector<const uint32_t*> bases(groups, groups + 3);
+  std::vector<uint32_t> ids(c.n_taps);
+  std::vector<uint64_t> offs(c.n_taps);
+  for (size_t t = 0; t < c.n_taps; t++) {
+    ids[t] = c.tap(t).group;
+    offs[t] = uint64_t(c.tap(t).offset) * rows + ((report->first_row - c.tap(t).back) & uint32_t(rows - 1));
+  }
+  auto* d_taps = static_cast<uint32_t*>(scratch(c.n_taps * 4, kSlotRowsTaps));
+  gather_words(s, d_taps, reinterpret_cast<const uint32_t* const*>(upload(bases, kSlotRowsBases)),
+               upload(ids, kSlotRowsIds), reinterpret_cast<const uint64_t*>(upload(offs, kSlotRowsOffs)), c.n_taps);
+  std::vector<uint32_t> taps(c.n_taps);
+  d2h(taps.data(), d_taps, c.n_taps * 4);
+  if (!h_mix && c.mix_size) {
+    hm.resize(c.mix_size);
+    d2h(hm.data(), mix, c.mix_size * 4);
+    h_mix = hm.data();
+  }
+  if (!h_global && c.output_size) {
+    hg.resize(c.output_size);
+    d2h(hg.data(), global, c.output_size * 4);
+    h_global = hg.data();
+  }
+  report->first_term = constraint_term(c, taps.data(), h_mix, h_global, poly_mix);
+}
+
+namespace {
+thread_local bool t_witness_check = false;
+
+// four field words from the OS for a check that must not touch the transcript
+FpExt os_random_ext() {
+  uint32_t w[8];
+  os_random_key(w);
+  return FpExt{{w[0] % kP, w[1] % kP, w[2] % kP, w[3] % kP}};
+}
+}  // namespace
+
+bool witness_check_mode() noexcept { return t_witness_check; }
+bool set_witness_check_mode(bool on) noexcept {
+  const bool was = t_witness_check;
+  t_witness_check = on;
+  return was;
+}
+FpExt constraint_rows_poly_mix(const uint32_t* h_poly_mix) {
+  return h_poly_mix ? fe_from_words(h_poly_mix) : os_random_ext();
 }
 
 namespace {
@@ -759,6 +860,26 @@ std::vector<uint32_t> prove_segment(const CircuitDef& c, int suite, uint32_t po2
   if (mix_out) *mix_out = mix;
   DevBuf dmix(mix.size() ? mix.size() : 1);
   upload_async(dmix.p, mix.data(), mix.size() * 4);
+  // r0hip_set_witness_check: the three groups are in their final form (the data commit
+  // interpolated out of place, the accumulation only read the data): the constraint polynomial on
+  // their rows, with a poly_mix of the OS's, so the transcript and the seal are those of the mode
+  // off. A violated row ends the proof here, before the accum commit and the 4N work.
+  auto check_witness = [&](const uint32_t* accum_group) {
+    if (!witness_check_mode()) return;
+    gate(0);
+    gate(1);
+    const uint32_t* wg[3] = {accum_group, code, data};
+    r0hip_constraint_report rep;
+    constraint_rows_run(c, po2, wg, dmix.p, global, mix.data(), header.data(), constraint_rows_poly_mix(nullptr),
+                        nullptr, &rep);
+    prof.mark("check_witness");
+    if (rep.bad_rows) {
+      (void)prof.finish();  // an expected outcome: the marks' events are released
+      throw std::runtime_error("constraint check failed: " + std::to_string(rep.bad_rows) + " of " +
+                               std::to_string(p.cycles) + " rows, first at cycle " + std::to_string(rep.first_row) +
+                               " (term " + std::to_string(rep.first_term) + ")");
+    }
+  };
   if (acc) {
     Span acc_span("accumulate");
     const size_t rows = p.cycles, cols = c.group_size(0);
@@ -776,8 +897,13 @@ std::vector<uint32_t> prove_segment(const CircuitDef& c, int suite, uint32_t po2
     }
     if (!acc->zeroed) eltwise_zeroize(s, acc->accum, rows * cols);
     prof.mark("accumulate");
+    check_witness(acc->accum);
     p.commit_group(0, acc->accum);  // nothing to wait for: the group never uploads
   } else {
+    if (witness_check_mode()) {
+      gate(2);
+      check_witness(accum);
+    }
     commit(0, 2, accum);
   }
   prof.mark("commit_accum");

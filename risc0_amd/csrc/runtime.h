@@ -16,6 +16,7 @@
 struct r0hip_bigint_back;  // include/r0hip.h
 struct r0hip_recursion_program;
 struct r0hip_opening;
+struct r0hip_constraint_report;
 
 #define HIP_OK(expr)                                                                          \
   do {                                                                                        \
@@ -135,6 +136,14 @@ enum ScratchSlot : int {
   // the injector as Back records (api.cpp): the records and their payload words
   kSlotRvBackRecs = 93,
   kSlotRvBackWords = 94,
+  // the constraint-rows check (prover.cpp): the report words, the first bad row's gathered taps
+  // and the gather's tables; its kernels' tables and scratch reuse the eval_check slots, which
+  // nothing else holds while the check runs
+  kSlotRowsReport = 95,
+  kSlotRowsTaps = 96,
+  kSlotRowsBases = 97,
+  kSlotRowsIds = 98,
+  kSlotRowsOffs = 99,
 };
 
 // Scratch buffer reused across calls (grown on demand; stream-ordered use only).
@@ -317,6 +326,29 @@ void merkle_open(hipStream_t s, int suite, const uint32_t* d_words, size_t n_wor
 // once through the thread's staging arena, the table and the outputs come from its pool.
 void merkle_open_host(int suite, const uint32_t* h_words, size_t n_words, const r0hip_opening* h_open, size_t n_open,
                       uint32_t* h_digests, uint32_t* h_status);
+
+// The constraint-rows check (prover.cpp; r0hip_constraint_rows): the circuit's constraint
+// polynomial on the 2^po2 rows of the witness groups as they are (accum, code, data: device
+// matrices, column-major), with poly_mix given. vals: where the per-row values go (2^po2 FpExt,
+// AoS), or null for thread scratch. The report names the bad rows; when there are any, the first
+// one's taps are gathered to the host and constraint_term (verify.cpp) names the term, from host
+// copies of mix and global (read back when null). Drains the thread's stream.
+struct CircuitDef;
+void constraint_rows_run(const CircuitDef& c, size_t po2, const uint32_t* const* groups, const uint32_t* mix,
+                         const uint32_t* global, const uint32_t* h_mix, const uint32_t* h_global, FpExt poly_mix,
+                         uint32_t* vals, r0hip_constraint_report* report);
+int32_t constraint_term(const CircuitDef& c, const uint32_t* taps, const uint32_t* mix, const uint32_t* global,
+                        FpExt poly_mix);
+// r0hip_set_witness_check: the calling thread's mode (off on every new thread). While it is on,
+// prove_segment runs constraint_rows_run on its three groups in their final form, before the
+// accum group is committed, and throws "constraint check failed: ..." instead of proving a
+// witness that violates a constraint.
+bool witness_check_mode() noexcept;
+bool set_witness_check_mode(bool on) noexcept;  // returns the previous mode
+// rows_report (eltwise.hip): over n FpExt values, out[0..1] = how many are nonzero (64 bits),
+// out[2] = the smallest nonzero index, out[3..19) = the 16 smallest in ascending order
+// (0xFFFFFFFF where there is none); 19 words.
+void rows_report(hipStream_t s, const uint32_t* vals, size_t n, uint32_t* out);
 
 // Element-wise and polynomial kernels (eltwise.hip).
 void eltwise_add(hipStream_t s, uint32_t* out, const uint32_t* a, const uint32_t* b, size_t n);

@@ -32,11 +32,13 @@ namespace r0 {
 // the out-of-domain point from the tap evaluations, by running the circuit's flattened program
 // (CircuitDef::ir, from <c>.poly.ir) over FpExt. mix/global are Montgomery words; eval_u holds
 // one value per tap in tap order.
-FpExt poly_ext(const CircuitDef& c, const uint32_t* mix, const uint32_t* global, const FpExt* eval_u,
-               FpExt poly_mix) {
-  std::vector<FpExt> pows(c.n_poly_mix);
+// The program run once: val[id] of every value, pows[k] of every poly_mix power; returns the id
+// the `r` record names.
+static uint32_t poly_ext_values(const CircuitDef& c, const uint32_t* mix, const uint32_t* global, const FpExt* eval_u,
+                                FpExt poly_mix, std::vector<FpExt>& val, std::vector<FpExt>& pows) {
+  pows.resize(c.n_poly_mix);
   for (size_t k = 0; k < c.n_poly_mix; k++) pows[k] = fe_pow(poly_mix, c.poly_mix_powers[k]);
-  std::vector<FpExt> val(c.n_ir);
+  val.assign(c.n_ir, fe_zero());
   for (size_t k = 0; k < c.n_ir; k++) {
     const uint32_t* r = c.ir + 6 * k;
     FpExt& v = val[r[1]];
@@ -50,11 +52,58 @@ FpExt poly_ext(const CircuitDef& c, const uint32_t* mix, const uint32_t* global,
       case 6: v = fe_mul(val[r[2]], val[r[3]]); break;
       case 7: v = fe_add(val[r[2]], fe_mul(val[r[3]], pows[r[4]])); break;  // a: acc + x * mix^k
       case 8: v = fe_add(val[r[2]], fe_mul(fe_mul(val[r[3]], val[r[4]]), pows[r[5]])); break;
-      case 9: return v;  // r: result (the record names the value in its dst slot)
+      case 9: return r[1];  // r: result (the record names the value in its dst slot)
       default: throw std::runtime_error("r0hip: bad constraint program record");
     }
   }
   throw std::runtime_error("r0hip: constraint program has no result");
+}
+
+FpExt poly_ext(const CircuitDef& c, const uint32_t* mix, const uint32_t* global, const FpExt* eval_u,
+               FpExt poly_mix) {
+  std::vector<FpExt> val, pows;
+  return val[poly_ext_values(c, mix, global, eval_u, poly_mix, val, pows)];
+}
+
+// Which term of the constraint program one trace row violates (r0hip_constraint_term). taps:
+// the row's tap values, one base-field Montgomery word per tap in tap order. The accumulate
+// chain that ends at the result (each `a`/`b` record's first operand is the chain's previous
+// link) is walked in chain order, first link first, for the first link that adds a nonzero
+// amount: x * mix^k for an `a`, x * y * mix^k for a `b`. An `a` is a single constraint and its
+// id is the answer. A `b` is a guarded block: the walk repeats inside the operand that is
+// itself an accumulate chain, and the innermost id found is the answer (the `b`'s own id when
+// neither operand is a chain, or when no link inside adds anything). -1: no term is violated.
+// The ids are those of the committed <circuit>.poly.ir.
+int32_t constraint_term(const CircuitDef& c, const uint32_t* taps, const uint32_t* mix, const uint32_t* global,
+                        FpExt poly_mix) {
+  std::vector<FpExt> eval_u(c.n_taps);
+  for (size_t i = 0; i < c.n_taps; i++) eval_u[i] = fe_from_fp(taps[i]);
+  std::vector<FpExt> val, pows;
+  const uint32_t res = poly_ext_values(c, mix, global, eval_u.data(), poly_mix, val, pows);
+  std::vector<const uint32_t*> rec(c.n_ir, nullptr);  // by id
+  for (size_t k = 0; k < c.n_ir; k++)
+    if (c.ir[6 * k] != 9) rec[c.ir[6 * k + 1]] = c.ir + 6 * k;
+  auto is_acc = [&](uint32_t id) { return rec[id] && (rec[id][0] == 7 || rec[id][0] == 8); };
+  auto nonzero = [](FpExt v) { return (v.c[0] | v.c[1] | v.c[2] | v.c[3]) != 0; };
+  // the first link of the chain ending at `end` that adds a nonzero amount, or -1
+  auto first_link = [&](uint32_t end) -> int32_t {
+    std::vector<uint32_t> chain;
+    for (uint32_t id = end; is_acc(id); id = rec[id][2]) chain.push_back(id);
+    for (size_t i = chain.size(); i-- > 0;) {
+      const uint32_t* r = rec[chain[i]];
+      const FpExt add = r[0] == 7 ? fe_mul(val[r[3]], pows[r[4]]) : fe_mul(fe_mul(val[r[3]], val[r[4]]), pows[r[5]]);
+      if (nonzero(add)) return int32_t(chain[i]);
+    }
+    return -1;
+  };
+  int32_t term = first_link(res);
+  while (term >= 0 && rec[term][0] == 8) {
+    const uint32_t* r = rec[term];
+    const int32_t inner = is_acc(r[3]) ? first_link(r[3]) : (is_acc(r[4]) ? first_link(r[4]) : -1);
+    if (inner < 0) break;
+    term = inner;
+  }
+  return term;
 }
 
 namespace {
@@ -197,6 +246,25 @@ extern "C" const char* r0hip_testing_verify_seal_structure_on(int where, const c
                                                               const uint32_t* seal, size_t seal_len,
                                                               uint32_t* po2_out) {
   return verify_entry_on(where, circuit, suite, seal, seal_len, false, nullptr, 0, nullptr, po2_out);
+}
+
+extern "C" const char* r0hip_constraint_term(const char* circuit, const uint32_t* h_taps, const uint32_t* h_mix,
+                                             const uint32_t* h_global, const uint32_t* h_poly_mix, int32_t* term) {
+  try {
+    const CircuitDef* c = find_circuit(circuit ? circuit : "");
+    R0_REQUIRE(c, std::string("r0hip_constraint_term: unknown circuit ") + (circuit ? circuit : "(null)"));
+    R0_REQUIRE(h_taps, "r0hip_constraint_term: h_taps is NULL");
+    R0_REQUIRE(h_mix, "r0hip_constraint_term: h_mix is NULL");
+    R0_REQUIRE(h_global, "r0hip_constraint_term: h_global is NULL");
+    R0_REQUIRE(h_poly_mix, "r0hip_constraint_term: h_poly_mix is NULL");
+    R0_REQUIRE(term, "r0hip_constraint_term: term is NULL");
+    *term = constraint_term(*c, h_taps, h_mix, h_global, vfy::load_ext(h_poly_mix));
+    return nullptr;
+  } catch (const std::exception& e) {
+    return strdup(e.what());
+  } catch (...) {
+    return strdup("r0hip: unknown error");
+  }
 }
 
 extern "C" const char* r0hip_poly_ext(const char* circuit, const uint32_t* h_mix, const uint32_t* h_global,

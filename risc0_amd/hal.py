@@ -69,6 +69,10 @@ def _declare(L):
         "r0hip_testing_verify_seal_structure_on": [C.c_int, C.c_char_p, C.c_int, u32p, sz, C.POINTER(C.c_uint32)],
         "r0hip_merkle_open_digests": [C.c_int, u32p, sz, vp, sz, u32p, u32p],
         "r0hip_poly_ext": [C.c_char_p, u32p, u32p, u32p, u32p, u32p],
+        "r0hip_constraint_rows": [C.c_char_p, C.c_uint32, vp, vp, vp, vp, vp, u32p, vp, vp],
+        "r0hip_constraint_term": [C.c_char_p, u32p, u32p, u32p, u32p, C.POINTER(C.c_int32)],
+        "r0hip_set_witness_check": [C.c_int, C.POINTER(C.c_int)],
+        "r0hip_worker_set_witness_check": [vp, C.c_int],
         "r0hip_synchronize": [],
         "r0hip_set_deferred": [C.c_int, C.POINTER(C.c_int)],
         "r0hip_set_proof_streams": [C.c_uint32, C.POINTER(C.c_uint32)],
@@ -143,6 +147,8 @@ def _declare(L):
         "r0hip_trim": [],
     }
     for name, args in sig.items():
+        if os.environ.get("R0HIP_LIB") and not hasattr(L, name):
+            continue  # an older build under R0HIP_LIB (tools/ A/B runs): calling what it lacks raises
         f = getattr(L, name)
         f.argtypes = args
         f.restype = C.c_void_p
@@ -262,6 +268,22 @@ class HipHal:
             yield self
         finally:
             set_proof_streams(was)
+
+    # ---- constraint check of the witness inside the provers (r0hip_set_witness_check) ----
+    def set_witness_check(self, on):
+        return set_witness_check(on)
+
+    @contextlib.contextmanager
+    def witness_check(self, on=True):
+        """`with hal.witness_check():` the mode for a block of calls, restored after it"""
+        was = set_witness_check(on)
+        try:
+            yield self
+        finally:
+            set_witness_check(was)
+
+    def constraint_rows(self, circuit, po2, code, data, accum, mix, glob, poly_mix=None, out=None):
+        return constraint_rows(circuit, po2, code, data, accum, mix, glob, poly_mix, out)
 
     # ---- allocation (hal/mod.rs:67-100) ----
     def alloc_elem(self, name, size):
@@ -1178,6 +1200,11 @@ class Worker:
             raise R0HipError("the worker is closed")
         return self._h
 
+    def set_witness_check(self, on):
+        """r0hip_worker_set_witness_check: the jobs submitted from now on are checked (or not) as
+        set_witness_check checks a proof; a violated job fails alone with the check's message"""
+        check(lib().r0hip_worker_set_witness_check(self._handle(), 1 if on else 0))
+
     def _submit(self, job, mix_words, keep):
         seal = np.zeros(self.seal_cap, dtype=np.uint32)
         mix = np.zeros(mix_words, dtype=np.uint32)
@@ -1416,6 +1443,50 @@ def poly_ext(circuit, mix, glob, eval_u, poly_mix):
     out = np.zeros(4, np.uint32)
     check(lib().r0hip_poly_ext(circuit.encode(), *(a.ctypes.data_as(u32p) for a in arrs), out.ctypes.data_as(u32p)))
     return out
+
+
+class ConstraintReport(C.Structure):
+    """struct r0hip_constraint_report"""
+    _fields_ = [("bad_rows", C.c_uint64), ("first_row", C.c_uint32), ("first_term", C.c_int32),
+                ("n_rows", C.c_uint32), ("rows", C.c_uint32 * 16)]
+
+
+def constraint_rows(circuit, po2, code, data, accum, mix, glob, poly_mix=None, out=None):
+    """r0hip_constraint_rows: the circuit's constraint polynomial on the 2^po2 rows of the witness
+    groups (device Buffers, as prove_segment takes them; mix and glob device Buffers as eval_check
+    takes them). poly_mix: 4 Montgomery words, None draws them from the OS. out: an optional
+    Buffer of 2^po2 FpExt that receives every row's value. Returns a dict: bad_rows, first_row
+    (None if no row is bad), first_term (the .poly.ir id, None if no row is bad) and rows (the
+    first 16 bad rows, ascending). A violated witness is a result, not an error."""
+    rep = ConstraintReport()
+    pm = None if poly_mix is None else np.ascontiguousarray(poly_mix, dtype=np.uint32)
+    ptr = lambda b: None if b is None else C.c_void_p(b.ptr if isinstance(b, Buffer) else b)
+    check(lib().r0hip_constraint_rows(circuit.encode() if circuit is not None else None, po2, ptr(code), ptr(data),
+                                      ptr(accum), ptr(mix), ptr(glob),
+                                      None if pm is None else pm.ctypes.data_as(u32p), ptr(out), C.byref(rep)))
+    bad = int(rep.bad_rows)
+    return {"bad_rows": bad, "first_row": int(rep.first_row) if bad else None,
+            "first_term": int(rep.first_term) if bad else None, "rows": [int(r) for r in rep.rows[:rep.n_rows]]}
+
+
+def constraint_term(circuit, taps, mix, glob, poly_mix):
+    """r0hip_constraint_term (host-only, no GPU): the id in <circuit>.poly.ir of the first term
+    that one row's tap values (Montgomery words, tap order) violate, or None if there is none."""
+    arrs = [None if a is None else np.ascontiguousarray(a, dtype=np.uint32) for a in (taps, mix, glob, poly_mix)]
+    term = C.c_int32(-1)
+    check(lib().r0hip_constraint_term(circuit.encode() if circuit is not None else None,
+                                      *(None if a is None else a.ctypes.data_as(u32p) for a in arrs), C.byref(term)))
+    return None if term.value < 0 else int(term.value)
+
+
+def set_witness_check(on):
+    """r0hip_set_witness_check: while on, the provers of the calling thread check the constraint
+    polynomial on the trace rows before the accum commit and raise R0HipError("constraint check
+    failed: K of N rows, first at cycle R (term T)") instead of proving a violated witness.
+    Returns the previous mode."""
+    was = C.c_int(0)
+    check(lib().r0hip_set_witness_check(1 if on else 0, C.byref(was)))
+    return bool(was.value)
 
 
 def libc_free(p):

@@ -29,6 +29,12 @@ REDC per sum ("fuse"), and tap addressing by column base pointers ("wide").
 Usage: gen_eval_check.py CIRCUIT OUTDIR [BUDGET]
 Writes OUTDIR/eval_check_<circuit>_k<i>.hip (one per kernel, compiled in parallel)
 and OUTDIR/eval_check_<circuit>.hip (launcher).
+
+A second family from the same program, OUTDIR/rows_<circuit>_k<i>.hip and OUTDIR/rows_<circuit>.hip
+(constraint_rows_<circuit>, emit(rows=True)): poly_fp on the N trace rows themselves, taps at
+(row - back) & (N - 1), no vanishing-polynomial scale, one FpExt per row (AoS) as the result. It
+is zero exactly on the rows that satisfy every constraint (r0hip_constraint_rows). It reads no
+tuning file; the eval_check family's text does not depend on it.
 """
 import os
 import sys
@@ -554,9 +560,20 @@ def uniform_fn(pg):
     return L
 
 
-def emit(circuit, outdir, budget, host=False):
+def emit(circuit, outdir, budget, host=False, rows=False):
+    """rows=False: the eval_check family (the 4N evaluation domain, tuned by <circuit>.ectune.json).
+    rows=True: the constraint-rows family (rows_<circuit>*.hip, namespace rows_<circuit>): the same
+    program on the N trace rows themselves. A tap is read at (row - back) & (N - 1), there is no
+    1/(x^N - 1) scale, and the last kernel leaves poly_fp(row) as one FpExt per row (AoS) in
+    A.acc. No tuning file applies: the default split at `budget`, no chosen materialisation,
+    two waves per SIMD, canonical results and 64-bit sums of products in every kernel."""
     pg = Program(circuit)
-    pg.mat = set(mat_config(circuit, budget))
+    pg.mat = set() if rows else set(mat_config(circuit, budget))
+    ns = f"rows_{circuit}" if rows else f"ec_{circuit}"
+    back_step = 1 if rows else 4
+    entry = f"constraint_rows_{circuit}" if rows else f"eval_check_{circuit}"  # entry point (evalcheck.h)
+    stem = f"rows_{circuit}" if rows else f"eval_check_{circuit}"       # file names
+    hostfn = f"rows_host_{circuit}" if rows else f"ec_host_{circuit}"
     terms, kernels = schedule(pg, budget)
     if HOIST:
         pg.hoist_uniform(terms)
@@ -572,14 +589,14 @@ def emit(circuit, outdir, budget, host=False):
             nuse[r] = nuse.get(r, 0) + 2
     for v in pg.mat:
         nuse[v] = nuse.get(v, 0) + 2
-    tune0 = kernel_config(circuit, budget)
-    resplit, piece_tune = resplit_config(circuit, budget)
+    tune0 = {} if rows else kernel_config(circuit, budget)
+    resplit, piece_tune = ({}, {}) if rows else resplit_config(circuit, budget)
     tune = {}
     split_kernels = []
     for k, items in enumerate(kernels):
         pieces = repack(pg, items, resplit[k]) if k in resplit else [items]
         for j, piece in enumerate(pieces):
-            t = dict(tune0.get(k, {}))
+            t = {"fuse": 1} if rows else dict(tune0.get(k, {}))
             if len(pieces) > 1:
                 t.update(piece_tune.get(f"{k}.{j}", {}))
             tune[len(split_kernels)] = t
@@ -618,7 +635,7 @@ def emit(circuit, outdir, budget, host=False):
         "#define EC_FN __device__ __forceinline__",
         "#endif",
         "namespace r0 {",
-        f"namespace ec_{circuit} {{",
+        f"namespace {ns} {{",
         "struct Args {",
         f"  const uint32_t* a[{nargs}];",
         "  const uint32_t* const* cp;  // column base pointers (kColArg/kColIdx order)",
@@ -1346,14 +1363,14 @@ def emit(circuit, outdir, budget, host=False):
                 # po2 <= 22), the column-pointer table above (211 columns x 2^26 points at
                 # po2=24); each kernel is instantiated for both, the launcher picks by domain
                 g, col, back = ins[2], ins[3], ins[4]
-                w(f"  const uint32_t v{i} = tap<W>(A.a[{g}], A.cp, {colslot[(g, col)]}u, {col}u, A.domain, (cycle - {4 * back}u) & mask);")
+                w(f"  const uint32_t v{i} = tap<W>(A.a[{g}], A.cp, {colslot[(g, col)]}u, {col}u, A.domain, (cycle - {back_step * back}u) & mask);")
                 Mv[i] = PM
                 continue
             if op == "l":
                 back = ins[4]
                 if back not in offs:
                     offs.add(back)
-                    w(f"  const uint32_t o{back} = ((cycle - {4 * back}u) & mask) * 4u;")
+                    w(f"  const uint32_t o{back} = ((cycle - {back_step * back}u) & mask) * 4u;")
                 w(f"  const uint32_t v{i} = ldc(A.cp[{colslot[(ins[2], ins[3])]}], o{back});")
                 Mv[i] = PM
                 continue
@@ -1422,7 +1439,10 @@ def emit(circuit, outdir, budget, host=False):
                 w(f"  const Acc s{sn + 2} = acc_add({cur}, s{sn + 1});")
                 sn, sb = sn + 2, sb2 + CANON
             w(f"  FpExt s = {canon_out(f's{sn}', sb)};")
-            if last:
+            if last and rows:
+                # poly_fp(row) itself: zero exactly where the row satisfies every constraint
+                w("  *accp = make_uint4(s.c[0], s.c[1], s.c[2], s.c[3]);")
+            elif last:
                 w("  s = fe_mul_fp(s, A.vinv[cycle & 3]);")
                 w("  #pragma unroll")
                 w("  for (int k = 0; k < 4; k++) A.check[uint64_t(k) * A.domain + cycle] = s.c[k];")
@@ -1440,12 +1460,12 @@ def emit(circuit, outdir, budget, host=False):
     head = (f"// GENERATED by tools/gen_eval_check.py from risc0_amd/circuits/{circuit}.poly.ir — do not edit.\n"
             + common_text)
     info = [
-        f"void eval_check_{circuit}_info(EvalCheckInfo* info) {{",
-        f"  info->combos = ec_{circuit}::kPmCombos; info->ncombos = {len(combo_index)}; info->npm = ec_{circuit}::NPM;",
+        f"void {entry}_info(EvalCheckInfo* info) {{",
+        f"  info->combos = {ns}::kPmCombos; info->ncombos = {len(combo_index)}; info->npm = {ns}::NPM;",
         f"  info->nargs = {nargs}; info->mat_fp = {nf}; info->mat_ext = {ne}; info->kernels = {len(kernels)};",
-        f"  info->modmuls_per_point = {modmuls(pg) + 4};",
-        f"  info->ncols = {len(colslot)}; info->col_arg = ec_{circuit}::kColArg; info->col_idx = ec_{circuit}::kColIdx;",
-        f"  info->n_uniform = ec_{circuit}::NUV; info->uniform = ec_{circuit}::uniform;",
+        f"  info->modmuls_per_point = {modmuls(pg) + (0 if rows else 4)};",
+        f"  info->ncols = {len(colslot)}; info->col_arg = {ns}::kColArg; info->col_idx = {ns}::kColIdx;",
+        f"  info->n_uniform = {ns}::NUV; info->uniform = {ns}::uniform;",
         "}",
     ]
     combos_line = f"const int kPmCombos[] = {{{', '.join(str(x) for x in flat) or '0'}}};"
@@ -1469,15 +1489,15 @@ def emit(circuit, outdir, budget, host=False):
         T.append(f"static void (*const kTable[NK])(const Args&, uint32_t) = {{{', '.join(f'k{i}' for i in range(len(bodies)))}}};")
         T.append(combos_line)
         T += uniform_fn(pg)
-        T.append(f"}}  // namespace ec_{circuit}")
+        T.append(f"}}  // namespace {ns}")
         T.append("}  // namespace r0")
         T += [
-            f'extern "C" int ec_host_{circuit}_combos(const int** combos, int* npm) {{',
-            f"  *combos = r0::ec_{circuit}::kPmCombos; *npm = r0::ec_{circuit}::NPM; return {len(combo_index)};",
+            f'extern "C" int {hostfn}_combos(const int** combos, int* npm) {{',
+            f"  *combos = r0::{ns}::kPmCombos; *npm = r0::{ns}::NPM; return {len(combo_index)};",
             "}",
-            f'extern "C" void ec_host_{circuit}(const uint32_t* const* args, const uint32_t* pm, const uint32_t* pmn,',
+            f'extern "C" void {hostfn}(const uint32_t* const* args, const uint32_t* pm, const uint32_t* pmn,',
             "    const uint32_t* vinv, uint32_t* acc, uint32_t* mf, uint32_t* me, uint32_t* check, uint32_t domain) {",
-            f"  using namespace r0::ec_{circuit};",
+            f"  using namespace r0::{ns};",
             "  Args A;",
             f"  for (int i = 0; i < {nargs}; i++) A.a[i] = args[i];",
             f"  const uint32_t* cp[{len(colslot)}];",
@@ -1510,9 +1530,9 @@ def emit(circuit, outdir, budget, host=False):
         K.append(f"    hipLaunchKernelGGL(k{ki}<false>, dim3(div_up(A.count, 256)), dim3(256), 0, s, A);")
         K.append("  HIP_OK(hipGetLastError());")
         K.append("}")
-        K.append(f"}}  // namespace ec_{circuit}")
+        K.append(f"}}  // namespace {ns}")
         K.append("}  // namespace r0")
-        with open(os.path.join(outdir, f"eval_check_{circuit}_k{ki}.hip"), "w") as f:
+        with open(os.path.join(outdir, f"{stem}_k{ki}.hip"), "w") as f:
             f.write("\n".join(K) + "\n")
     # kernels tuned to the scalar-column-base tap form at every size ("wide" in the tuning file)
     assert len(kernels) <= 64
@@ -1524,17 +1544,17 @@ def emit(circuit, outdir, budget, host=False):
         w(f"void launch_k{ki}(hipStream_t s, const Args& A);")
     w(combos_line)
     L += uniform_fn(pg)
-    w(f"}}  // namespace ec_{circuit}")
+    w(f"}}  // namespace {ns}")
     L += info
-    w(f"void eval_check_{circuit}(hipStream_t s, const EvalCheckArgs& e) {{")
-    w(f"  using namespace ec_{circuit};")
-    w(f"  R0_REQUIRE(e.nargs == {nargs}, \"eval_check_{circuit}: wrong argument count\");")
+    w(f"void {entry}(hipStream_t s, const EvalCheckArgs& e) {{")
+    w(f"  using namespace {ns};")
+    w(f"  R0_REQUIRE(e.nargs == {nargs}, \"{entry}: wrong argument count\");")
     w("  Args A;")
     w(f"  for (int i = 0; i < {nargs}; i++) A.a[i] = e.args[i];")
     w("  A.cp = e.colptr;")
     w("  A.pm = e.poly_mix; A.pmn = e.poly_mix_nb; A.acc = e.acc; A.check = e.check; A.vinv = e.vinv; A.domain = e.domain;")
     w("  A.mf = e.mat_fp; A.me = e.mat_ext; A.uv = e.uniform;")
-    w(f"  R0_REQUIRE(NUV == 0 || e.uniform, \"eval_check_{circuit}: no lane-independent value table\");")
+    w(f"  R0_REQUIRE(NUV == 0 || e.uniform, \"{entry}: no lane-independent value table\");")
     w(f"  A.wide = e.wide >= 0 ? uint64_t(e.wide) : {wide_default}ull;  // tuned: {wide_list}")
     w("  // tiles of e.tile points run every kernel before the next tile, so a tile's")
     w("  // trace columns are re-read from the Infinity Cache rather than HBM")
@@ -1547,19 +1567,22 @@ def emit(circuit, outdir, budget, host=False):
     w("  }")
     w("}")
     w("}  // namespace r0")
-    with open(os.path.join(outdir, f"eval_check_{circuit}.hip"), "w") as f:
+    with open(os.path.join(outdir, f"{stem}.hip"), "w") as f:
         f.write("\n".join(L) + "\n")
     tot = sum(stats)
     base = pg.cone_cost([pg.res])
-    print(f"{circuit}: {len(terms)} terms, {len(kernels)} kernels, mat {nf} Fp + {ne} FpExt, "
+    print(f"{circuit}{' (rows)' if rows else ''}: {len(terms)} terms, {len(kernels)} kernels, mat {nf} Fp + {ne} FpExt, "
           f"work {tot} vs {base} ({tot / base:.2f}x), per-kernel cost {stats}")
 
 
 if __name__ == "__main__":
-    if sys.argv[1] == "--host":
-        # gen_eval_check.py --host CIRCUIT OUT.cpp [BUDGET]
-        src = emit(sys.argv[2], None, int(sys.argv[4]) if len(sys.argv) > 4 else 4000, host=True)
+    if sys.argv[1] in ("--host", "--host-rows"):
+        # gen_eval_check.py --host CIRCUIT OUT.cpp [BUDGET]      (--host-rows: the rows family)
+        src = emit(sys.argv[2], None, int(sys.argv[4]) if len(sys.argv) > 4 else 4000, host=True,
+                   rows=sys.argv[1] == "--host-rows")
         with open(sys.argv[3], "w") as f:
             f.write(src)
     else:
         emit(sys.argv[1], sys.argv[2], int(sys.argv[3]) if len(sys.argv) > 3 else 4000)
+        # the constraint-rows family beside it, always at the default budget
+        emit(sys.argv[1], sys.argv[2], 4000, rows=True)
