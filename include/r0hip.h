@@ -885,8 +885,9 @@ const char* r0hip_testing_verify_seal_structure(const char* circuit, int suite, 
  * thread's pool, and the host compares each result with the tree's top layer, so the device
  * never decides a verdict. Verdicts, messages (the first failure in opening order), *po2_out and
  * the code root are those of the host check. Poseidon2 and SHA-256 run on the device;
- * Poseidon254 (suite 2) is accepted and runs the host openings, since a BN254 permutation per
- * lane has no measured device form. The device call always drains (also in deferred mode) and
+ * Poseidon254 (suite 2) is accepted and runs the host openings, unless
+ * r0hip_set_verify_device_poseidon254(1) was called (below): then its openings run on the device
+ * too, one per lane. The device call always drains (also in deferred mode) and
  * the thread keeps no device memory afterwards. Any other `where` is an error. */
 #define R0HIP_VERIFY_HOST 0
 #define R0HIP_VERIFY_DEVICE 1
@@ -894,6 +895,19 @@ const char* r0hip_testing_verify_seal_structure(const char* circuit, int suite, 
 const char* r0hip_verify_seal_on(int where, const char* circuit, int suite, const uint32_t* seal, size_t seal_len,
                                  const uint32_t* h_code_roots, size_t n_code_roots, uint32_t* h_code_root_out,
                                  uint32_t* po2_out);
+/* Poseidon254 openings on the device, behind a switch: process-wide, 0 by default, read at the
+ * time of each check by r0hip_verify_seal_on and r0hip_testing_verify_seal_structure_on with
+ * where = R0HIP_VERIFY_DEVICE, by r0hip_merkle_open_digests, and by verify = 2 in
+ * r0hip_prove_segments, r0hip_prove_trace_segments and the worker's verifier thread. With 1 a
+ * suite-2 seal's openings are hashed by one kernel (merkle_open_poseidon254, one opening per lane
+ * on the library's own BN254 code); verdicts, messages, *po2_out and the code root do not
+ * change. Each check reads the switch once, so a change made while a check runs takes effect
+ * with the next check. Measured: a modest gain for one receipt
+ * checked alone, none in a worker, where the switch trades receipt latency for host cores. With
+ * 0 every call behaves as if the switch did not exist. Any value but 0 or 1 is an error naming
+ * `on`. Needs no GPU and no r0hip_init. */
+/* [host-only] */
+const char* r0hip_set_verify_device_poseidon254(int on);
 /* TESTING ONLY, as r0hip_testing_verify_seal_structure is, with the openings host or device. */
 /* [drains] */
 const char* r0hip_testing_verify_seal_structure_on(int where, const char* circuit, int suite, const uint32_t* seal,
@@ -907,10 +921,13 @@ const char* r0hip_testing_verify_seal_structure_on(int where, const char* circui
  * case the verifier rejects as "non-canonical Poseidon2 digest word in seal" (the digest is then
  * written as zeros; the other openings are unaffected). The digests are byte for byte the host
  * verifier's (Poseidon2: sponge of rate 16, unpadded; SHA-256: the unpadded row hash over
- * little-endian words). suite 0 or 1; suite 2 has no device form and is an error here. Refused
- * on the host before any device call, naming the argument: a NULL array with a nonzero count,
- * cols outside [1, 256], levels above 40, a row or path range outside n_words, and (Poseidon2)
- * a row word >= p. Ranges may overlap and openings may share rows. */
+ * little-endian words). suite 0 or 1; suite 2 is an error here unless
+ * r0hip_set_verify_device_poseidon254(1) was called: then it is Poseidon254's unpadded_hash and
+ * hash_pair, path digests are any 256-bit words (reduced mod r as the host's hash_pair reduces
+ * them) and the status is always 0. Refused on the host before any device call, naming the
+ * argument: a NULL array with a nonzero count, cols outside [1, 256], levels above 40, a row or
+ * path range outside n_words, and (Poseidon2, Poseidon254) a row word >= p. Ranges may overlap
+ * and openings may share rows. */
 typedef struct r0hip_opening {
   uint64_t row_off;  /* first word of the row in h_words */
   uint64_t path_off; /* first word of the path: 8 words per level */

@@ -710,6 +710,8 @@ unsafe extern "C" {
         h_code_root_out: *mut u32,
         po2_out: *mut u32,
     ) -> *const c_char;
+    // process-wide, 0 by default: Poseidon254 openings of a device check on the device too
+    pub fn r0hip_set_verify_device_poseidon254(on: c_int) -> *const c_char;
     pub fn r0hip_testing_verify_seal_structure_on(
         where_: c_int,
         circuit: *const c_char,

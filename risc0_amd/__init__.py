@@ -14,7 +14,8 @@ from .hal import (POSEIDON2, POSEIDON254, SHA256, BigIntBack, Buffer, HipHal, R0
                   set_proof_streams, Back, BacksStruct, Backs, BacksJob, BACK_WORDS, rv32im_inject_backs,
                   prove_segment_trace_backs, RecursionProgram, CODE_ENCODED, CODE_MONTGOMERY,
                   WorkerProgramJobStruct, WorkerInputJobStruct, RecursionInputInfo, recursion_preflight,
-                  recursion_last_preflight_ms, Opening, merkle_open_digests, VERIFY_RECEIPTS_DEVICE, ConstraintReport,
+                  recursion_last_preflight_ms, Opening, merkle_open_digests, set_verify_device_poseidon254,
+                  VERIFY_RECEIPTS_DEVICE, ConstraintReport,
                   constraint_rows, constraint_term, set_witness_check)
 
 __all__ = ["POSEIDON2", "POSEIDON254", "SHA256", "BigIntBack", "bigint_accum_inject", "bigint_accum_states", "bigint_accum_states_device", "bigint_backs", "BIGINT_BACK_DTYPE", "prove_recursion", "recursion_witgen", "rv32im_witgen", "prove_segment_trace", "ResidentTrace", "prove_segment_trace_resident", "Buffer", "HipHal", "R0HipError", "check", "exported_symbols", "last_profile",
@@ -24,5 +25,6 @@ __all__ = ["POSEIDON2", "POSEIDON254", "SHA256", "BigIntBack", "bigint_accum_inj
            "Worker", "call_stats", "set_proof_streams", "Back", "BacksStruct", "Backs", "BacksJob", "BACK_WORDS",
            "rv32im_inject_backs", "prove_segment_trace_backs", "RecursionProgram", "CODE_ENCODED", "CODE_MONTGOMERY",
            "WorkerProgramJobStruct", "WorkerInputJobStruct", "RecursionInputInfo", "recursion_preflight",
-           "recursion_last_preflight_ms", "Opening", "merkle_open_digests", "VERIFY_RECEIPTS_DEVICE",
+           "recursion_last_preflight_ms", "Opening", "merkle_open_digests", "set_verify_device_poseidon254",
+           "VERIFY_RECEIPTS_DEVICE",
            "ConstraintReport", "constraint_rows", "constraint_term", "set_witness_check"]

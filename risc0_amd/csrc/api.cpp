@@ -398,21 +398,25 @@ const char* r0hip_merkle_open_digests(int suite, const uint32_t* h_words, size_t
                                       size_t n_open, uint32_t* h_digests, uint32_t* h_status) {
   return wrap([&] {
     // everything refused here and in merkle_open_check is refused before the first device call
-    R0_REQUIRE(suite == 0 || suite == 1, "merkle_open_digests: suite = " + std::to_string(suite) +
-                                             " has no device form (0 Poseidon2 or 1 SHA-256)");
+    const bool p254 = suite == 2 && verify_device_poseidon254();  // the switch, read once for this call
+    R0_REQUIRE(suite == 0 || suite == 1 || p254,
+               "merkle_open_digests: suite = " + std::to_string(suite) + " has no device form (0 Poseidon2 or 1 SHA-256" +
+                   (suite == 2 ? "; 2 Poseidon254 only after r0hip_set_verify_device_poseidon254(1))" : ")"));
     R0_REQUIRE(h_words || n_words == 0, "merkle_open_digests: h_words is NULL");
     R0_REQUIRE(h_open || n_open == 0, "merkle_open_digests: h_open is NULL");
     R0_REQUIRE(h_digests || n_open == 0, "merkle_open_digests: h_digests is NULL");
     R0_REQUIRE(h_status || n_open == 0, "merkle_open_digests: h_status is NULL");
-    merkle_open_check(suite, n_words, h_open, n_open);
-    if (suite == 0)  // the permutation's bounds assume field elements, as the verifier's read_elems guarantees
+    merkle_open_check(suite, n_words, h_open, n_open, p254);
+    // the permutation's bounds (Poseidon2) and p254_pack8's column bound (Poseidon254) assume field
+    // elements, as the verifier's read_elems guarantees
+    if (suite == 0 || suite == 2)
       for (size_t i = 0; i < n_open; i++)
         for (uint32_t k = 0; k < h_open[i].cols; k++)
           R0_REQUIRE(h_words[h_open[i].row_off + k] < kP,
                      "merkle_open_digests: h_words[" + std::to_string(h_open[i].row_off + k) + "] (row of h_open[" +
                          std::to_string(i) + "]) is not a canonical field element");
     if (!n_open) return;
-    merkle_open_host(suite, h_words, n_words, h_open, n_open, h_digests, h_status);
+    merkle_open_host(suite, h_words, n_words, h_open, n_open, h_digests, h_status, p254);
   });
 }
 const char* r0hip_scatter(uint32_t* d_into, const uint32_t* d_index, const uint32_t* d_offsets,

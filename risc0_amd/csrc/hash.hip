@@ -616,6 +616,61 @@ __global__ __launch_bounds__(kOpenThreads) void merkle_open_sha_kernel(uint32_t*
   status[i] = 0;
 }
 
+// Poseidon254 (taken only behind r0hip_set_verify_device_poseidon254): one opening per lane, the row
+// hash in p254_rows_kernel's form and the path on the host verifier's own p254_hash_pair. A BN254
+// permutation is ~76k dependent instructions, so a wave takes as long as its longest opening (a
+// 128-column row is 8 + 1 permutations, a path up to 15 more) whatever its lanes hold; 64-lane
+// workgroups put the 4-6 waves of a seal on CUs of their own. Row words are canonical (checked by
+// the callers); path digests are any 256-bit words, which p254_from_digest reduces as it does on
+// the host, so the status is always 0. One p254_hash_pair call site: the sides are chosen before it.
+__global__ __launch_bounds__(kOpenThreads) void merkle_open_p254_kernel(uint32_t* out, uint32_t* status,
+                                                                      const uint32_t* __restrict__ words,
+                                                                      const r0hip_opening* __restrict__ open,
+                                                                      uint32_t n_open) {
+  const uint32_t i = blockIdx.x * kOpenThreads + threadIdx.x;
+  if (i >= n_open) return;
+  const r0hip_opening o = open[i];
+  const uint32_t* path = words + o.path_off;
+  const uint32_t* row = words + o.row_off;
+  // the row hash as p254_rows_kernel has it, which is hash_elems(2, ...): Montgomery words
+  // decoded to canonical values, 8 to a cell, a cell past the row's end left zero
+  bn::Fr c[3] = {p254_zero(), p254_zero(), p254_zero()};
+#pragma unroll 1
+  for (uint32_t col = 0; col < o.cols; col += 16) {
+    uint32_t v[8];
+#pragma unroll
+    for (int k = 0; k < 8; k++) v[k] = col + k < o.cols ? mont_reduce(row[col + k]) : 0u;
+    c[1] = p254_pack8(v);
+    if (col + 8 < o.cols) {
+#pragma unroll
+      for (int k = 0; k < 8; k++) v[k] = col + 8 + k < o.cols ? mont_reduce(row[col + 8 + k]) : 0u;
+      c[2] = p254_pack8(v);
+    } else {
+      c[2] = p254_zero();
+    }
+    p254_mix(c);
+  }
+  uint32_t cur[8];
+  p254_to_digest(c[0], cur);
+  uint64_t idx = o.index;
+#pragma unroll 1
+  for (uint32_t l = 0; l < o.levels; l++) {
+    const bool low = idx & 1;
+    idx >>= 1;
+    uint32_t a[8], b[8];
+#pragma unroll
+    for (int k = 0; k < 8; k++) {
+      const uint32_t w = path[8 * l + k];
+      a[k] = low ? w : cur[k];
+      b[k] = low ? cur[k] : w;
+    }
+    p254_hash_pair(a, b, cur);
+  }
+#pragma unroll
+  for (int k = 0; k < 8; k++) out[uint64_t(i) * 8 + k] = cur[k];
+  status[i] = 0;
+}
+
 }  // namespace
 
 // Z_0 .. Z_levels for rows of `cols` columns ((levels + 1) * 8 words, cached): Z_0 is
@@ -871,9 +926,10 @@ void merkle_layers(hipStream_t s, int suite, uint32_t* nodes, size_t rows, size_
 // ---- Merkle openings of a seal (the kernels above) ----
 // Everything the kernels' loops and addresses depend on, checked on the host: a table that
 // passes can neither read outside [0, n_words) nor run longer than 16 + 40 hashes per opening.
-void merkle_open_check(int suite, size_t n_words, const r0hip_opening* h_open, size_t n_open) {
-  R0_REQUIRE(suite == 0 || suite == 1, "merkle_open: suite " + std::to_string(suite) +
-                                           " has no device form (Poseidon2 and SHA-256 only)");
+void merkle_open_check(int suite, size_t n_words, const r0hip_opening* h_open, size_t n_open, bool allow_p254) {
+  R0_REQUIRE(suite == 0 || suite == 1 || (suite == 2 && allow_p254),
+             "merkle_open: suite " + std::to_string(suite) + " has no device form (Poseidon2 and SHA-256 only" +
+                 (suite == 2 ? "; Poseidon254 only after r0hip_set_verify_device_poseidon254(1))" : ")"));
   R0_REQUIRE(n_open < (size_t(1) << 24), "merkle_open: n_open = " + std::to_string(n_open) + " is too large");
   R0_REQUIRE(h_open || n_open == 0, "merkle_open: h_open is NULL");
   for (size_t i = 0; i < n_open; i++) {
@@ -897,8 +953,8 @@ void merkle_open_check(int suite, size_t n_words, const r0hip_opening* h_open, s
 static bool open_quad() { return env_size("R0_MERKLE_OPEN_QUAD", 1) != 0; }
 
 void merkle_open(hipStream_t s, int suite, const uint32_t* d_words, size_t n_words, const r0hip_opening* h_open,
-                 size_t n_open, r0hip_opening* d_open, uint32_t* d_out) {
-  merkle_open_check(suite, n_words, h_open, n_open);
+                 size_t n_open, r0hip_opening* d_open, uint32_t* d_out, bool allow_p254) {
+  merkle_open_check(suite, n_words, h_open, n_open, allow_p254);
   if (n_open == 0) return;
   R0_REQUIRE(d_words && d_open && d_out, "merkle_open: null device pointer");
   upload_async(d_open, h_open, n_open * sizeof(r0hip_opening));
@@ -907,7 +963,8 @@ void merkle_open(hipStream_t s, int suite, const uint32_t* d_words, size_t n_wor
     hashes += (h_open[i].cols + 15) / 16 + h_open[i].levels;
     bytes += 4.0 * h_open[i].cols + 32.0 * h_open[i].levels + 36 + sizeof(r0hip_opening);
   }
-  KScope ks(suite == 0 ? "merkle_open_poseidon2" : "merkle_open_sha256", bytes, suite == 0 ? hashes * kP2Modmuls : 0);
+  static const char* const names[3] = {"merkle_open_poseidon2", "merkle_open_sha256", "merkle_open_poseidon254"};
+  KScope ks(names[suite], bytes, suite == 0 ? hashes * kP2Modmuls : 0);
   uint32_t* d_status = d_out + n_open * 8;
   const dim3 block(kOpenThreads);
   const uint32_t n = uint32_t(n_open);
@@ -917,6 +974,9 @@ void merkle_open(hipStream_t s, int suite, const uint32_t* d_words, size_t n_wor
   else if (suite == 0)
     hipLaunchKernelGGL(merkle_open_p2_lane_kernel, dim3(div_up(n_open, kOpenThreads)), block, 0, s, d_out, d_status,
                        d_words, d_open, n);
+  else if (suite == 2)
+    hipLaunchKernelGGL(merkle_open_p254_kernel, dim3(div_up(n_open, kOpenThreads)), block, 0, s, d_out, d_status,
+                       d_words, d_open, n);
   else
     hipLaunchKernelGGL(merkle_open_sha_kernel, dim3(div_up(n_open, kOpenThreads)), block, 0, s, d_out, d_status,
                        d_words, d_open, n);
@@ -924,12 +984,13 @@ void merkle_open(hipStream_t s, int suite, const uint32_t* d_words, size_t n_wor
 }
 
 void merkle_open_host(int suite, const uint32_t* h_words, size_t n_words, const r0hip_opening* h_open, size_t n_open,
-                      uint32_t* h_digests, uint32_t* h_status) {
-  merkle_open_check(suite, n_words, h_open, n_open);  // before the first device call
+                      uint32_t* h_digests, uint32_t* h_status, bool allow_p254) {
+  merkle_open_check(suite, n_words, h_open, n_open, allow_p254);  // before the first device call
   if (n_open == 0) return;
   DevBuf words(n_words), table(n_open * (sizeof(r0hip_opening) / 4)), out(n_open * 9);
   upload_async(words.p, h_words, n_words * 4);
-  merkle_open(stream(), suite, words.p, n_words, h_open, n_open, reinterpret_cast<r0hip_opening*>(table.p), out.p);
+  merkle_open(stream(), suite, words.p, n_words, h_open, n_open, reinterpret_cast<r0hip_opening*>(table.p), out.p,
+              allow_p254);
   std::vector<uint32_t> got(n_open * 9);
   download(got.data(), out.p, got.size() * 4);
   memcpy(h_digests, got.data(), n_open * 32);

@@ -317,15 +317,23 @@ void merkle_layers(hipStream_t s, int suite, uint32_t* nodes, size_t rows, size_
 // checks the host copy of the table (merkle_open_check: cols in [1, 256], levels <= 40, every range
 // inside n_words; throws before any device call), uploads it to d_open and queues one kernel on s:
 // d_out gets 8 digest words per opening, then one status word per opening (0 computed, 2 a
-// Poseidon2 path digest word >= p). Poseidon2 row words must be canonical (< p).
+// Poseidon2 path digest word >= p). Poseidon2 row words must be canonical (< p). Suite 2
+// (Poseidon254, one opening per lane: the row hash as p254_rows_kernel has it, Montgomery words
+// decoded first as hash_elems(2, ...) decodes them, the path on p254_hash_pair) is taken only with
+// allow_p254, which the caller sets from verify_device_poseidon254() once per check, so a switch
+// flipped by another thread in mid-check changes nothing of that check. Its row words must be
+// canonical too, its path digests are any 256-bit words (p254_from_digest reduces them, as on the
+// host) and its status is always 0.
 constexpr uint32_t kMerkleOpenMaxCols = 256, kMerkleOpenMaxLevels = 40;
-void merkle_open_check(int suite, size_t n_words, const r0hip_opening* h_open, size_t n_open);
+// r0hip_set_verify_device_poseidon254: process-wide, off by default, read at each check (verify.cpp).
+bool verify_device_poseidon254();
+void merkle_open_check(int suite, size_t n_words, const r0hip_opening* h_open, size_t n_open, bool allow_p254 = false);
 void merkle_open(hipStream_t s, int suite, const uint32_t* d_words, size_t n_words, const r0hip_opening* h_open,
-                 size_t n_open, r0hip_opening* d_open, uint32_t* d_out);
+                 size_t n_open, r0hip_opening* d_open, uint32_t* d_out, bool allow_p254 = false);
 // Host arrays in and out on the calling thread's stream, complete on return: the words go up
 // once through the thread's staging arena, the table and the outputs come from its pool.
 void merkle_open_host(int suite, const uint32_t* h_words, size_t n_words, const r0hip_opening* h_open, size_t n_open,
-                      uint32_t* h_digests, uint32_t* h_status);
+                      uint32_t* h_digests, uint32_t* h_status, bool allow_p254 = false);
 
 // The constraint-rows check (prover.cpp; r0hip_constraint_rows): the circuit's constraint
 // polynomial on the 2^po2 rows of the witness groups as they are (accum, code, data: device

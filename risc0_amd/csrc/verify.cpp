@@ -14,6 +14,7 @@
 // Host code only — no HIP call, so it runs without a GPU; the one exception is opt-in:
 // r0hip_verify_seal_on(R0HIP_VERIFY_DEVICE, ...) hands the deferred Merkle openings to the device
 // (device_openings below), everything else of the check staying here.
+#include <atomic>
 #include <cstdlib>
 #include <cstring>
 #include <stdexcept>
@@ -26,6 +27,10 @@
 #include "verify_core.h"
 
 namespace r0 {
+
+// r0hip_set_verify_device_poseidon254: whether a device check takes Poseidon254 openings too
+static std::atomic<int> g_verify_device_p254{0};
+bool verify_device_poseidon254() { return g_verify_device_p254.load(std::memory_order_relaxed) != 0; }
 
 // PolyExt::poly_ext (the circuits' generated poly_ext.rs, e.g. circuit/recursion/src/poly_ext.rs,
 // as called by verify_validity, zkp/src/verify/mod.rs:356-386): the constraint polynomial at
@@ -111,7 +116,8 @@ using namespace vfy;
 
 // The device opening backend (r0hip_verify_seal_on with R0HIP_VERIFY_DEVICE): the pending list as
 // an r0hip_opening table over the seal words, hashed by merkle_open_host on the calling thread's
-// stream. The launcher checks every range again and refuses on the host.
+// stream. The launcher checks every range again and refuses on the host. Suite 2 gets here only
+// when verify_entry_on found the Poseidon254 switch on, so it is allowed here without a second read.
 void device_openings(int suite, const uint32_t* words, size_t n_words, const std::vector<PendingOpening>& pending,
                      OpeningResult* out) {
   const size_t n = pending.size();
@@ -127,7 +133,7 @@ void device_openings(int suite, const uint32_t* words, size_t n_words, const std
     table[i].levels = uint32_t(p.tree->path_levels(p.idx));
   }
   std::vector<uint32_t> digests(n * 8), status(n);
-  merkle_open_host(suite, words, n_words, table.data(), n, digests.data(), status.data());
+  merkle_open_host(suite, words, n_words, table.data(), n, digests.data(), status.data(), /*allow_p254=*/true);
   for (size_t i = 0; i < n; i++) {
     out[i].cur = digest_of(&digests[8 * i]);
     out[i].status = status[i];
@@ -145,6 +151,15 @@ uint32_t verify_seal(const CircuitDef& c, int suite, const uint32_t* seal, size_
   ReadIOP iop(seal, len, suite);
   iop.defer = true;  // openings hashed after the transcript, on several threads (check_pending)
   iop.backend = backend;  // or in one device launch
+  // Poseidon254 with its openings on the device: the 31 pair hashes above each tree's top layer
+  // (7 trees) stay serial on this thread, as in the host check. R0_VERIFY_P254_TOPS=1 (read at each
+  // check, as R0_MERKLE_OPEN_QUAD is) deals them over the opening threads instead (hash_tops):
+  // measured and not kept as the default, the thread starts cost more than the hashes (DESIGN.md
+  // section 7 item 4).
+  if (backend && suite == 2) {
+    const char* e = std::getenv("R0_VERIFY_P254_TOPS");
+    if (e && std::strtol(e, nullptr, 10) != 0) iop.top_threads = verify_threads();
+  }
   uint32_t psi[16], ci[16];
   for (int i = 0; i < 16; i++) {
     psi[i] = fp_encode(uint8_t(PROOF_SYSTEM_INFO[i]));
@@ -216,9 +231,9 @@ extern "C" const char* r0hip_testing_verify_seal_structure(const char* circuit, 
 }
 
 // where = DEVICE: the host check with the device opening backend. Poseidon254 keeps the host
-// openings (no device form). The call drains and hands the thread's memory back, as every entry
-// point that gives the host a verdict does (api.cpp wrap); nothing here creates a stream on a
-// path that launches nothing.
+// openings unless r0hip_set_verify_device_poseidon254 is on, read here. The call drains and hands
+// the thread's memory back, as every entry point that gives the host a verdict does (api.cpp
+// wrap); nothing here creates a stream on a path that launches nothing.
 static const char* verify_entry_on(int where, const char* circuit, int suite, const uint32_t* seal, size_t seal_len,
                                    bool check_validity, const uint32_t* code_roots, size_t n_code_roots,
                                    uint32_t* code_root_out, uint32_t* po2_out) {
@@ -228,7 +243,8 @@ static const char* verify_entry_on(int where, const char* circuit, int suite, co
     return strdup(("r0hip: where = " + std::to_string(where) + " is neither R0HIP_VERIFY_HOST nor R0HIP_VERIFY_DEVICE")
                       .c_str());
   const char* err = verify_entry(circuit, suite, seal, seal_len, check_validity, code_roots, n_code_roots,
-                                 code_root_out, po2_out, suite == 2 ? nullptr : device_openings);
+                                 code_root_out, po2_out,
+                                 suite == 2 && !verify_device_poseidon254() ? nullptr : device_openings);
   drain_after_error();  // a throw may have left work queued; a clean return has drained already
   call_drained();
   release_thread_memory();
@@ -246,6 +262,13 @@ extern "C" const char* r0hip_testing_verify_seal_structure_on(int where, const c
                                                               const uint32_t* seal, size_t seal_len,
                                                               uint32_t* po2_out) {
   return verify_entry_on(where, circuit, suite, seal, seal_len, false, nullptr, 0, nullptr, po2_out);
+}
+
+extern "C" const char* r0hip_set_verify_device_poseidon254(int on) {
+  if (on != 0 && on != 1)
+    return strdup(("r0hip_set_verify_device_poseidon254: on = " + std::to_string(on) + " is neither 0 nor 1").c_str());
+  g_verify_device_p254.store(on, std::memory_order_relaxed);
+  return nullptr;
 }
 
 extern "C" const char* r0hip_constraint_term(const char* circuit, const uint32_t* h_taps, const uint32_t* h_mix,

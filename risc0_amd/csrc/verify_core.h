@@ -10,9 +10,11 @@
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
+#include <exception>
 #include <memory>
 #include <stdexcept>
 #include <string>
+#include <system_error>
 #include <thread>
 #include <vector>
 
@@ -60,6 +62,57 @@ Digest hash_pair(int suite, const Digest& a, const Digest& b) {
   return p2_hash_words(both, 16);
 }
 
+// The nodes above a tree's top layer (merkle.rs:105-118), heap order: rest[i] for 1 <= i <
+// top.size() is the hash of its two children, which are top-layer digests for i >= top.size() / 2
+// and rest[2i], rest[2i + 1] below that; rest[0] is unused. threads <= 1 is the serial loop of the
+// reference. With more, each level's pair hashes (top.size() / 2, then half as many, ...) are
+// dealt over up to `threads` host threads while a level has at least 4 of them, and the last
+// levels run on the caller: the same hashes of the same inputs, so the same rest[]. A thread's
+// exception (a Poseidon2 word >= p) is rethrown on the caller, the one the serial loop meets first.
+inline void hash_tops(int suite, const std::vector<Digest>& top, unsigned threads, std::vector<Digest>& rest) {
+  const size_t top_size = top.size();
+  rest.assign(top_size, Digest{});
+  auto node = [&](size_t i) {
+    rest[i] = i >= top_size / 2 ? hash_pair(suite, top[2 * i - top_size], top[2 * i + 1 - top_size])
+                                : hash_pair(suite, rest[2 * i], rest[2 * i + 1]);
+  };
+  for (size_t lo = top_size / 2; lo >= 1; lo /= 2) {  // the level's nodes are [lo, 2 lo)
+    const unsigned use = unsigned(std::min<size_t>(threads, lo));
+    if (use <= 1 || lo < 4) {
+      for (size_t i = 2 * lo; i-- > lo;) node(i);
+      continue;
+    }
+    std::vector<std::exception_ptr> err(use);
+    std::vector<size_t> err_at(use, 0);
+    auto work = [&](unsigned t) {
+      for (size_t i = 2 * lo - 1 - t; i >= lo; i -= use) {  // downwards as the serial loop; i >= lo >= use
+        try {
+          node(i);
+        } catch (...) {
+          err[t] = std::current_exception();
+          err_at[t] = i;
+          return;
+        }
+      }
+    };
+    std::vector<std::thread> pool;
+    pool.reserve(use);
+    unsigned started = 1;  // the caller is worker 0; a thread that cannot be created leaves its share here
+    try {
+      for (; started < use; started++) pool.emplace_back(work, started);
+    } catch (const std::system_error&) {
+    }
+    work(0);
+    for (unsigned t = started; t < use; t++) work(t);
+    for (auto& th : pool) th.join();
+    size_t first = 0;
+    unsigned which = 0;
+    for (unsigned t = 0; t < use; t++)
+      if (err_at[t] > first) first = err_at[t], which = t;
+    if (first) std::rethrow_exception(err[which]);
+  }
+}
+
 struct MerkleVerifier;
 // A Merkle opening read from the seal whose hashes are checked later (ReadIOP::defer): the
 // transcript never depends on a hash of an opening, so the query loop reads and checks the
@@ -91,6 +144,7 @@ struct ReadIOP {
   bool defer = false;  // Merkle openings go to `pending` instead of being hashed at once
   std::vector<PendingOpening> pending;
   OpeningBackend backend = nullptr;  // null: check_pending hashes the openings on host threads
+  unsigned top_threads = 0;  // > 1: the trees' top layers are hashed by hash_tops on that many threads
   ReadIOP(const uint32_t* w, size_t n, int s) : words(w), size(n), suite(s), rng(make_rng(s)) {}
   const uint32_t* read(size_t n) {
     if (n > size - pos) throw VerifyError("seal too short");
@@ -125,10 +179,14 @@ struct MerkleVerifier {
     top_size = size_t(1) << top_layer;
     const uint32_t* t = iop.read(top_size * 8);
     for (size_t i = 0; i < top_size; i++) top.push_back(digest_of(t + 8 * i));
-    rest.resize(top_size);
-    for (size_t i = top_size; i-- > top_size / 2;)
-      rest[i] = hash_pair(iop.suite, top[2 * i - top_size], top[2 * i + 1 - top_size]);
-    for (size_t i = top_size / 2; i-- > 1;) rest[i] = hash_pair(iop.suite, rest[2 * i], rest[2 * i + 1]);
+    if (iop.top_threads > 1) {
+      hash_tops(iop.suite, top, iop.top_threads, rest);
+    } else {
+      rest.resize(top_size);
+      for (size_t i = top_size; i-- > top_size / 2;)
+        rest[i] = hash_pair(iop.suite, top[2 * i - top_size], top[2 * i + 1 - top_size]);
+      for (size_t i = top_size / 2; i-- > 1;) rest[i] = hash_pair(iop.suite, rest[2 * i], rest[2 * i + 1]);
+    }
     root = top_size > 1 ? rest[1] : top[0];
     iop.commit(root);
   }

@@ -68,6 +68,7 @@ def _declare(L):
         "r0hip_verify_seal_on": [C.c_int, C.c_char_p, C.c_int, u32p, sz, u32p, sz, u32p, C.POINTER(C.c_uint32)],
         "r0hip_testing_verify_seal_structure_on": [C.c_int, C.c_char_p, C.c_int, u32p, sz, C.POINTER(C.c_uint32)],
         "r0hip_merkle_open_digests": [C.c_int, u32p, sz, vp, sz, u32p, u32p],
+        "r0hip_set_verify_device_poseidon254": [C.c_int],
         "r0hip_poly_ext": [C.c_char_p, u32p, u32p, u32p, u32p, u32p],
         "r0hip_constraint_rows": [C.c_char_p, C.c_uint32, vp, vp, vp, vp, vp, u32p, vp, vp],
         "r0hip_constraint_term": [C.c_char_p, u32p, u32p, u32p, u32p, C.POINTER(C.c_int32)],
@@ -1386,7 +1387,8 @@ def merkle_open_digests(suite, words, openings):
     """r0hip_merkle_open_digests: the device step of the receipt check by itself. `openings` is a
     list of (row_off, path_off, index, cols, levels) over the u32 array `words`; returns
     (digests [n, 8], status [n]): per opening the row hash folded up its path, and 0 or 2 (a
-    Poseidon2 path digest word >= p). Suites Poseidon2 and SHA-256."""
+    Poseidon2 path digest word >= p). Suites Poseidon2 and SHA-256, and Poseidon254 while
+    set_verify_device_poseidon254(1) holds."""
     words = np.ascontiguousarray(words, dtype=np.uint32)
     sid = SUITES[suite] if isinstance(suite, str) else suite
     n = len(openings)
@@ -1397,6 +1399,14 @@ def merkle_open_digests(suite, words, openings):
     check(lib().r0hip_merkle_open_digests(sid, words.ctypes.data_as(u32p), words.size, C.cast(table, C.c_void_p), n,
                                           digests.ctypes.data_as(u32p), status.ctypes.data_as(u32p)))
     return digests, status
+
+
+def set_verify_device_poseidon254(on):
+    """r0hip_set_verify_device_poseidon254: process-wide and off by default. While on, a device
+    receipt check (verify_seal(where="device"), verify=2 in the pipelines and the worker) and
+    merkle_open_digests take Poseidon254 openings on the GPU as well; verdicts and messages are the
+    host check's. `on` is 0 or 1 (False or True); needs no GPU."""
+    check(lib().r0hip_set_verify_device_poseidon254(int(on)))
 
 
 VERIFY_WHERE = {"host": 0, "device": 1}  # R0HIP_VERIFY_HOST, R0HIP_VERIFY_DEVICE

@@ -15,6 +15,14 @@ behaviour without the option and the baseline of each comparison.
   (b) pipeline   r0hip_prove_trace_segments over the session's --segments (12) po2-20 segments at
                  3 in flight with verify = 1 against 2: ms per segment and the mean verify_ms.
   (c) latency    one segment at 1 in flight, verify = 1 against 2: prove_ms + verify_ms.
+  (d) p254       Poseidon254, whose device openings sit behind r0hip_set_verify_device_poseidon254
+                 (the device legs turn it on for their call and off again): one recursion seal at
+                 --rec-po2 from the GPU prover, host against device and against device with the trees'
+                 top layers hashed level by level on the verifier's threads (R0_VERIFY_P254_TOPS=1,
+                 hash_tops; the default is the serial loop), with the kernel's own time; and
+                 --p254-jobs (12) Poseidon254 recursion jobs of that size through a worker at 3 in
+                 flight, verify = 1 against 2: wall ms per job and the mean verify_ms. This part alone
+                 (--only p254) writes profiles/verify_device_p254_ab.json.
 
 Per comparison: each leg's repeats, median, min and max, the host leg's spread (max - min), the
 device leg's gain (host median - device median) and whether the gain exceeds the spread (the rule
@@ -22,7 +30,7 @@ by which a change counts as a gain). One JSON file (default profiles/verify_devi
 same line on stdout.
 
     python3 tools/bench_verify_openings.py [--po2 20] [--rec-po2 18] [--segments 12] [--repeats 7]
-                                           [--warmups 2] [--only seals,pipeline,latency] [--out FILE]
+                                           [--warmups 2] [--only seals,pipeline,latency,p254] [--out FILE]
 """
 import argparse
 import ctypes as C
@@ -35,7 +43,7 @@ import time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
-PARTS = ("seals", "pipeline", "latency")
+PARTS = ("seals", "pipeline", "latency", "p254")
 
 
 def parse():
@@ -46,9 +54,14 @@ def parse():
     ap.add_argument("--repeats", type=int, default=7, help="timed repeats of each leg (at least 5)")
     ap.add_argument("--warmups", type=int, default=2, help="untimed rounds of each leg before the timed ones")
     ap.add_argument("--only", default=",".join(PARTS), help="comma-separated parts")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "verify_device_ab.json"))
+    ap.add_argument("--p254-jobs", type=int, default=12, help="recursion jobs the worker of (d) proves per repeat")
+    ap.add_argument("--out", default=None, help="default profiles/verify_device_ab.json, or "
+                                                "profiles/verify_device_p254_ab.json with --only p254")
     args = ap.parse_args()
     args.only = [w for w in args.only.split(",") if w]
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles",
+                                "verify_device_p254_ab.json" if args.only == ["p254"] else "verify_device_ab.json")
     if args.repeats < 5 or any(w not in PARTS for w in args.only):
         ap.error("--repeats must be at least 5, --only a list of " + ", ".join(PARTS))
     return args
@@ -82,16 +95,23 @@ def alternate(args, legs):
 
 
 def seal_legs(args, r, circuit, suite, seal, po2):
-    def timed(where, quad):
+    def timed(where, quad, tops=False):
         def run():
             os.environ["R0_MERKLE_OPEN_QUAD"] = "1" if quad else "0"
-            t = time.perf_counter()
-            assert r.verify_seal(circuit, suite, seal, where=where) == po2
-            return 1000.0 * (time.perf_counter() - t)
+            os.environ["R0_VERIFY_P254_TOPS"] = "1" if tops else "0"
+            r.set_verify_device_poseidon254(suite == 2 and where == "device")
+            try:
+                t = time.perf_counter()
+                assert r.verify_seal(circuit, suite, seal, where=where) == po2
+                return 1000.0 * (time.perf_counter() - t)
+            finally:
+                r.set_verify_device_poseidon254(0)
         return run
     legs = {"host": timed("host", True), "device": timed("device", True)}
     if suite == 0:
         legs["device_lane"] = timed("device", False)
+    if suite == 2:  # the trees' top layers on the verifier's threads (hash_tops) instead of the serial loop
+        legs["device_hash_tops"] = timed("device", True, tops=True)
     got = alternate(args, legs)
     out = {name: summary(ms) for name, ms in got.items()}
     for name in [n for n in legs if n != "host"]:  # the kernel's own time
@@ -104,6 +124,7 @@ def seal_legs(args, r, circuit, suite, seal, po2):
         out[name]["kernel"] = kname
         out[name]["kernel_ms"] = round(ms / calls, 4)
     os.environ["R0_MERKLE_OPEN_QUAD"] = "1"
+    os.environ.pop("R0_VERIFY_P254_TOPS", None)
     out["seal_words"] = int(seal.size)
     print(f"  {circuit} po2={po2} suite={suite}: " + "  ".join(
         f"{n}: {out[n]['median']} ms" + (f" (kernel {out[n]['kernel_ms']})" if "kernel_ms" in out[n] else "")
@@ -120,11 +141,13 @@ def main():
     hal = r.HipHal("poseidon2")
     result = {}
     t0 = time.perf_counter()
-    mine = list(range(args.segments if "pipeline" in args.only else 1))
-    jobs, tr0 = bench.session_jobs(r, argparse.Namespace(po2=args.po2, session=args.segments), mine)
-    print(f"{len(jobs)} po2={args.po2} session segment(s) built in {time.perf_counter() - t0:.1f} s", file=sys.stderr,
-          flush=True)
-    job = jobs[0]
+    jobs = []
+    if set(args.only) & {"seals", "pipeline", "latency"}:
+        mine = list(range(args.segments if "pipeline" in args.only else 1))
+        jobs, tr0 = bench.session_jobs(r, argparse.Namespace(po2=args.po2, session=args.segments), mine)
+        print(f"{len(jobs)} po2={args.po2} session segment(s) built in {time.perf_counter() - t0:.1f} s",
+              file=sys.stderr, flush=True)
+        job = jobs[0]
 
     if "seals" in args.only:
         seals = {}
@@ -170,12 +193,52 @@ def main():
         result["latency"] = compare(out, "host", ["device"])
         print(f"  latency: host {out['host']['median']} device {out['device']['median']} ms", file=sys.stderr, flush=True)
 
+    if "p254" in args.only:
+        import recursion_program as RP
+        po2 = args.rec_po2
+        prog, inp = RP.random_program(np.random.default_rng(0x5249534330), (1 << po2) - RP.ZK_CYCLES - 1)
+        wom, cyc, iops = (np.ascontiguousarray(np.asarray(a, dtype=np.uint32).reshape(-1))
+                          for a in RP.trace_arrays(RP.preflight(prog, inp)))
+        ctrl_words = RP.ctrl_group(prog, po2)
+        h254 = r.HipHal("poseidon254")
+        ctrl = h254.copy_from_elem("ctrl", ctrl_words)
+        seal = r.prove_recursion(h254, po2, ctrl, wom, cyc, iops, 0x5EED)[0]
+        ctrl.free()
+        out = {"recursion_poseidon254": seal_legs(args, r, "recursion", 2, seal, po2)}
+
+        def worker(verify):
+            def run():
+                r.set_verify_device_poseidon254(verify == 2)
+                try:
+                    t = time.perf_counter()
+                    with r.Worker(hal, max_po2=po2, in_flight=3, verify=verify) as w:
+                        for _ in range(args.p254_jobs):
+                            w.submit_recursion(po2, ctrl_words, wom, cyc, iops, suite="poseidon254")
+                        res = [w.wait(600.0) for _ in range(args.p254_jobs)]
+                    wall = 1000.0 * (time.perf_counter() - t)
+                finally:
+                    r.set_verify_device_poseidon254(0)
+                assert all(x is not None and x[3] is None for x in res), [x and x[3] for x in res]
+                return wall / args.p254_jobs, statistics.mean(x[4] for x in res)
+            return run
+
+        got = alternate(args, {"host": worker(1), "device": worker(2)})
+        wk = {leg: dict(summary([x[0] for x in v]), verify_ms_mean=round(statistics.mean(x[1] for x in v), 3))
+              for leg, v in got.items()}
+        wk["what"] = (f"wall ms per job (worker created and destroyed inside the timed span), {args.p254_jobs} "
+                      f"Poseidon254 recursion jobs of po2 {po2} at 3 in flight")
+        out["worker"] = compare(wk, "host", ["device"])
+        print(f"  p254 worker: host {wk['host']['median']} device {wk['device']['median']} ms/job, verify_ms "
+              f"{wk['host']['verify_ms_mean']} -> {wk['device']['verify_ms_mean']}", file=sys.stderr, flush=True)
+        result["p254"] = out
+
     buf, total = C.create_string_buffer(256), C.c_uint64(0)
     r.check(r.lib().r0hip_device_info(buf, 256, C.byref(total)))
     out = {
         "what": "the receipt check with the seal's Merkle openings on host threads (host: r0hip_verify_seal, "
                 "verify = 1) against one device launch (device: r0hip_verify_seal_on(DEVICE), verify = 2; "
-                "device_lane: the Poseidon2 kernel with one opening per lane instead of one per lane quad). "
+                "device_lane: the Poseidon2 kernel with one opening per lane instead of one per lane quad; p254: "
+                "Poseidon254, the device legs under r0hip_set_verify_device_poseidon254(1)). "
                 "Legs alternated in one process after warm-up rounds of each",
         "device": buf.value.decode(), "po2": args.po2, "rec_po2": args.rec_po2, "repeats": args.repeats,
         "warmup_rounds": args.warmups, "verify_threads": os.environ.get("R0HIP_VERIFY_THREADS", "default (up to 8)"),
