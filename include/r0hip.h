@@ -825,7 +825,8 @@ typedef struct r0hip_worker_program_job {
  * only the allow-list is read. Submit refuses a NULL handle, a suite or po2 that is not the
  * handle's, po2 above max_po2, and takes a use count that lasts until the job can be handed back.
  * The preflight runs on the uploader thread while the provers work, into page-locked buffers of
- * the job's set; its failure lands in this job's error alone. With verify and no allow-list the
+ * the job's set (or on a pool thread, r0hip_worker_set_preflight_threads below); its failure lands
+ * in this job's error alone. With verify and no allow-list the
  * seal is checked against the handle's control id. */
 #define R0HIP_JOB_RECURSION_INPUT 4
 typedef struct r0hip_worker_input_job {
@@ -853,6 +854,37 @@ const char* r0hip_worker_destroy(r0hip_worker* w);
  * other jobs are untouched, and a passing job's seal is that of the switch off. */
 /* [host-only] */
 const char* r0hip_worker_set_witness_check(r0hip_worker* w, int on);
+/* Kind-4 preflights on a pool of host threads. n = 0 (the default): the uploader thread runs each
+ * kind-4 job's preflight itself, one at a time, and stages nothing else meanwhile. n = 1..8: n
+ * pool threads run the preflights of queued kind-4 jobs ahead of the uploader, in ticket order,
+ * each into one of n + in_flight + 1 slots of page-locked buffers (the look-ahead is bounded by
+ * the slots); r0hip_worker_submit hands such a job to the pool as well as to the FIFO and still
+ * touches no device; the uploader, on reaching the job, only waits for its preflight and points
+ * the job's set at the slot, and the set's prover returns the slot once its stream has drained.
+ * A pool thread never uses the device: no stream, no kernel, no copy, only the page-locked
+ * allocation and free of its slot. A job whose handle has no plan yet when a pool thread takes it
+ * is left to the uploader, which makes the plan and runs the preflight as with n = 0; call
+ * r0hip_recursion_program_prepare_input first to have every job on the pool. Seals, mixes,
+ * outputs, error messages and the order in which jobs start are those of n = 0. Refused, changing
+ * nothing: w == NULL, n > 8, and a call while a job is outstanding (submitted and not yet handed
+ * back by r0hip_worker_wait). *was (optional) receives the previous n. r0hip_worker_destroy joins
+ * the pool threads and frees the slots. */
+/* [host-only] */
+const char* r0hip_worker_set_preflight_threads(r0hip_worker* w, uint32_t n, uint32_t* was);
+/* Which way the worker's kind-4 preflights went, since r0hip_worker_create (peak_slots_in_use:
+ * since the last change of n). Any thread, at any time before destroy. out_size must be
+ * sizeof(r0hip_worker_stats). */
+typedef struct r0hip_worker_stats {
+  uint32_t preflight_threads, preflight_slots, peak_slots_in_use, reserved;
+  uint64_t pool_jobs;      /* kind-4 preflights run by the pool */
+  uint64_t inline_jobs;    /* kind-4 preflights run by the uploader */
+  uint64_t slot_bytes;     /* page-locked bytes the slots hold now */
+  double pool_busy_ms;               /* summed over pool threads, inside preflights */
+  double uploader_preflight_ms;      /* uploader time inside inline preflights */
+  double uploader_wait_preflight_ms; /* uploader time waiting for the pool */
+} r0hip_worker_stats;
+/* [host-only] */
+const char* r0hip_worker_get_stats(r0hip_worker* w, r0hip_worker_stats* out, size_t out_size);
 
 /* ---- seal verification (risc0/zkp/src/verify/mod.rs:500-560 `verify`, with merkle.rs:79-186,
  * fri.rs:36-155, read_iop.rs:20-84; rv32im seals lead with the version word 2,

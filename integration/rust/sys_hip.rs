@@ -202,6 +202,22 @@ pub struct R0HipWorkerInputJob {
     pub n_output: usize,
 }
 
+/// Which way the worker's kind-4 preflights went (struct r0hip_worker_stats).
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct R0HipWorkerStats {
+    pub preflight_threads: u32,
+    pub preflight_slots: u32,
+    pub peak_slots_in_use: u32,
+    pub reserved: u32,
+    pub pool_jobs: u64,
+    pub inline_jobs: u64,
+    pub slot_bytes: u64,
+    pub pool_busy_ms: f64,
+    pub uploader_preflight_ms: f64,
+    pub uploader_wait_preflight_ms: f64,
+}
+
 /// What r0hip_recursion_program_prepare_input made (struct r0hip_recursion_input_info).
 #[repr(C)]
 pub struct R0HipRecursionInputInfo {
@@ -679,6 +695,11 @@ unsafe extern "C" {
     pub fn r0hip_worker_destroy(w: *mut R0HipWorker) -> *const c_char;
     // the witness check for the jobs submitted from now on (recorded at submit)
     pub fn r0hip_worker_set_witness_check(w: *mut R0HipWorker, on: c_int) -> *const c_char;
+    // kind-4 preflights on n pool threads (0..8; 0: on the uploader thread, the default); refused
+    // while a job is outstanding. `was` may be null.
+    pub fn r0hip_worker_set_preflight_threads(w: *mut R0HipWorker, n: u32, was: *mut u32) -> *const c_char;
+    // out_size: size_of::<R0HipWorkerStats>()
+    pub fn r0hip_worker_get_stats(w: *mut R0HipWorker, out: *mut R0HipWorkerStats, out_size: usize) -> *const c_char;
 
     // ---- verification (host-only) ----
     pub fn r0hip_verify_seal(

@@ -13,7 +13,7 @@ from .hal import (POSEIDON2, POSEIDON254, SHA256, BigIntBack, Buffer, HipHal, R0
                   fill_chacha20, prove_recursion_keyed, RecursionInput, WorkerJobStruct, Worker, call_stats,
                   set_proof_streams, Back, BacksStruct, Backs, BacksJob, BACK_WORDS, rv32im_inject_backs,
                   prove_segment_trace_backs, RecursionProgram, CODE_ENCODED, CODE_MONTGOMERY,
-                  WorkerProgramJobStruct, WorkerInputJobStruct, RecursionInputInfo, recursion_preflight,
+                  WorkerProgramJobStruct, WorkerInputJobStruct, WorkerStats, RecursionInputInfo, recursion_preflight,
                   recursion_last_preflight_ms, Opening, merkle_open_digests, set_verify_device_poseidon254,
                   VERIFY_RECEIPTS_DEVICE, ConstraintReport,
                   constraint_rows, constraint_term, set_witness_check)
@@ -24,7 +24,7 @@ __all__ = ["POSEIDON2", "POSEIDON254", "SHA256", "BigIntBack", "bigint_accum_inj
            "host_array", "pinned_copy", "fill_chacha20", "prove_recursion_keyed", "RecursionInput", "WorkerJobStruct",
            "Worker", "call_stats", "set_proof_streams", "Back", "BacksStruct", "Backs", "BacksJob", "BACK_WORDS",
            "rv32im_inject_backs", "prove_segment_trace_backs", "RecursionProgram", "CODE_ENCODED", "CODE_MONTGOMERY",
-           "WorkerProgramJobStruct", "WorkerInputJobStruct", "RecursionInputInfo", "recursion_preflight",
+           "WorkerProgramJobStruct", "WorkerInputJobStruct", "WorkerStats", "RecursionInputInfo", "recursion_preflight",
            "recursion_last_preflight_ms", "Opening", "merkle_open_digests", "set_verify_device_poseidon254",
            "VERIFY_RECEIPTS_DEVICE",
            "ConstraintReport", "constraint_rows", "constraint_term", "set_witness_check"]

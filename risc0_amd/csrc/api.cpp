@@ -808,6 +808,12 @@ RecursionInputCounts recursion_program_prepare_input(const r0hip_recursion_progr
   return RecursionInputCounts{h->ops.n_wom, h->ops.n_iops, h->ops.n_output};
 }
 
+bool recursion_program_planned_counts(const r0hip_recursion_program* h, RecursionInputCounts* out) {
+  if (!h->planned.load(std::memory_order_acquire)) return false;
+  *out = RecursionInputCounts{h->ops.n_wom, h->ops.n_iops, h->ops.n_output};
+  return true;
+}
+
 void recursion_program_preflight_into(const r0hip_recursion_program* h, const uint32_t* h_input, size_t n_input,
                                       uint32_t* wom, uint32_t* iops, uint32_t* output) {
   rpf::run(h->ops, h_input, n_input, wom, iops, output);

@@ -19,6 +19,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <algorithm>
+#include <atomic>
 #include <chrono>
 #include <deque>
 #include <functional>
@@ -33,6 +34,7 @@
 #include "backs.h"
 #include "circuit.h"
 #include "devmem.h"
+#include "preflight_pool.h"
 #include "runtime.h"
 
 namespace r0 {
@@ -426,20 +428,33 @@ struct PinnedWords {
   ~PinnedWords() {
     if (p) (void)hipHostFree(p);
   }
-  void reserve(size_t n) {
+  void reserve(size_t n, unsigned flags = hipHostMallocDefault) {
     if (n <= words) return;
     if (p) (void)hipHostFree(p);
     p = nullptr, words = 0;
     void* q = nullptr;
-    HIP_OK(hipHostMalloc(&q, n * 4, hipHostMallocDefault));
+    HIP_OK(hipHostMalloc(&q, n * 4, flags));
     p = static_cast<uint32_t*>(q), words = n;
   }
+};
+
+// one slot of the worker's preflight pool (preflight_pool.h): what a set holds for a kind-4 job,
+// owned by the pool so a preflight can run before its job has a set. `bytes` is what get_stats
+// reads while a pool thread grows the slot.
+struct PfSlot {
+  PinnedWords wom, iops;
+  std::vector<uint32_t> out;
+  std::atomic<uint64_t> bytes{0};
 };
 
 struct WorkerSet : TraceSet {
   DevBuf ctrl;  // recursion jobs: the control group (allocated at the set's first one)
   PinnedWords pf_wom, pf_iops;  // kind-4 jobs: the preflight's WOM and IOP values
   std::vector<uint32_t> pf_out;
+  // where wjob's preflight is: the set's own buffers above (the uploader ran it) or those of the
+  // pool's slot pf_slot, which the prover gives back once its stream has drained
+  const uint32_t *pf_wom_p = nullptr, *pf_iops_p = nullptr;
+  long pf_slot = -1;
   r0hip_worker_job* wjob = nullptr;
   bool witness_check = false;  // wjob's r0hip_worker_set_witness_check mode, as recorded at its submit
   size_t cap_inj = 0, cap_txn = 0, cap_big = 0;  // entries, records, bytes
@@ -486,6 +501,45 @@ struct WorkerImpl {
   std::deque<std::pair<r0hip_worker_job*, std::vector<uint32_t>>> vq;
   std::thread uploader, verifier;
   std::vector<std::thread> provers;
+  // r0hip_worker_set_preflight_threads: the pool that runs kind-4 preflights ahead of the uploader
+  // and the queued jobs it was given at submit (under mu, as checked_jobs); the uploader's own
+  // counters for r0hip_worker_get_stats
+  using PfPool = PreflightPool<r0hip_worker_job, PfSlot>;
+  PfPool pool{pool_preflight, [] { return new PfSlot; }, [](PfSlot* s) { delete s; }};
+  std::set<const r0hip_worker_job*> pooled_jobs;
+  std::mutex stats_mu;
+  uint64_t inline_jobs = 0;
+  double uploader_preflight_ms = 0, uploader_wait_preflight_ms = 0;
+
+  // a kind-4 job's preflight, into (wom, iops, out); the job's output fields are written here
+  static void preflight_job(r0hip_worker_job* j, const RecursionInputCounts& cnt, PinnedWords& wom, PinnedWords& iops,
+                            std::vector<uint32_t>& out, unsigned host_flags) {
+    auto* ij = reinterpret_cast<r0hip_worker_input_job*>(j);
+    ij->n_output = cnt.n_output;
+    R0_REQUIRE(!ij->h_output || cnt.n_output <= ij->output_cap,
+               "recursion input job: output buffer too small: the program writes " + std::to_string(cnt.n_output) +
+                   " words");
+    wom.reserve(cnt.n_wom * 4 + 4, host_flags);
+    iops.reserve(cnt.n_iops * 4 + 4, host_flags);
+    out.resize(cnt.n_output);
+    recursion_program_preflight_into(job_program(j), ij->h_input, ij->n_input, wom.p, iops.p, out.data());
+    if (ij->h_output && cnt.n_output) memcpy(ij->h_output, out.data(), cnt.n_output * 4);
+  }
+
+  // on a pool thread, which never uses the device: no ensure_init, no stream, no copy. The only
+  // HIP calls are the page-locked allocation and free of the slot, portable because this thread
+  // has not chosen the library's device. A handle without a plan is left to the uploader, since
+  // making the plan drains the device; a failure (a throw) is the job's own.
+  static PoolVerdict pool_preflight(r0hip_worker_job* j, PfSlot& s, std::string*) {
+    RecursionInputCounts cnt;
+    if (!recursion_program_planned_counts(job_program(j), &cnt)) return PoolVerdict::kLeft;
+    struct Sized {  // also when the preflight throws after the slot grew
+      PfSlot& s;
+      ~Sized() { s.bytes.store((s.wom.words + s.iops.words) * 4, std::memory_order_relaxed); }
+    } sized{s};
+    preflight_job(j, cnt, s.wom, s.iops, s.out, hipHostMallocPortable);
+    return PoolVerdict::kReady;
+  }
 
   void finish(r0hip_worker_job* j) {
     // the job's proof has drained (or never ran): its hold on a resident program ends here,
@@ -550,7 +604,7 @@ struct WorkerImpl {
     for (;;) {
       r0hip_worker_job* j;
       BacksInfo info;
-      bool job_check = false;
+      bool job_check = false, job_pooled = false;
       {
         std::unique_lock<std::mutex> lk(mu);
         cv_in.wait(lk, [&] { return !fifo.empty() || stopping; });
@@ -559,6 +613,7 @@ struct WorkerImpl {
         info = fifo.front().second;
         fifo.pop_front();
         job_check = checked_jobs.erase(j) != 0;
+        job_pooled = pooled_jobs.erase(j) != 0;
       }
       const long s = free_q.get();
       WorkerSet& b = sets[s];
@@ -584,6 +639,20 @@ struct WorkerImpl {
         ok = false;
       }
       ready_q.put(s);  // the prover fills its groups while the inputs upload
+      // a job the pool was given is taken from it whatever happened above: the pool's queue is in
+      // ticket order, and a finished preflight's slot goes back through the set's prover
+      PfPool::Taken taken;
+      if (job_pooled) try {
+          const auto t0 = std::chrono::steady_clock::now();
+          taken = pool.take(j);
+          const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+          if (taken.verdict == PoolVerdict::kReady) b.pf_slot = taken.slot;
+          std::lock_guard<std::mutex> lk(stats_mu);
+          uploader_wait_preflight_ms += ms;
+        } catch (const std::exception& e) {
+          fail(e.what());
+          ok = false;
+        }
       if (ok) try {
           const size_t n = size_t(1) << j->po2;
           if (j->kind == R0HIP_JOB_RECURSION) {
@@ -597,18 +666,30 @@ struct WorkerImpl {
             // which its prover copies up itself. Nothing stays queued on this thread's stream: the
             // first job of a handle makes its plan here (a read-back, the run keys and their sort),
             // and recursion_program_prepare_input drains before it returns
-            auto* ij = reinterpret_cast<r0hip_worker_input_job*>(j);
-            const RecursionInputCounts cnt = recursion_program_prepare_input(job_program(j));
-            ij->n_output = cnt.n_output;
-            R0_REQUIRE(!ij->h_output || cnt.n_output <= ij->output_cap,
-                       "recursion input job: output buffer too small: the program writes " +
-                           std::to_string(cnt.n_output) + " words");
-            b.pf_wom.reserve(cnt.n_wom * 4 + 4);
-            b.pf_iops.reserve(cnt.n_iops * 4 + 4);
-            b.pf_out.resize(cnt.n_output);
-            recursion_program_preflight_into(job_program(j), ij->h_input, ij->n_input, b.pf_wom.p, b.pf_iops.p,
-                                             b.pf_out.data());
-            if (ij->h_output && cnt.n_output) memcpy(ij->h_output, b.pf_out.data(), cnt.n_output * 4);
+            // With a pool (r0hip_worker_set_preflight_threads) a pool thread has run it into a slot,
+            // output and failure included, and the set is pointed at the slot; only a job whose
+            // handle had no plan then is left to this thread
+            if (job_pooled && taken.verdict == PoolVerdict::kReady) {
+              PfSlot& slot = pool.slot(taken.slot);
+              b.pf_wom_p = slot.wom.p, b.pf_iops_p = slot.iops.p;
+            } else if (job_pooled && taken.verdict == PoolVerdict::kFailed) {
+              throw std::runtime_error(taken.error);
+            } else {
+              const RecursionInputCounts cnt = recursion_program_prepare_input(job_program(j));
+              struct Count {  // a failed preflight is counted too, as the pool counts its own
+                WorkerImpl& m;
+                std::chrono::steady_clock::time_point t0;
+                ~Count() {
+                  const double ms =
+                      std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+                  std::lock_guard<std::mutex> lk(m.stats_mu);
+                  m.inline_jobs++;
+                  m.uploader_preflight_ms += ms;
+                }
+              } count{*this, std::chrono::steady_clock::now()};
+              preflight_job(j, cnt, b.pf_wom, b.pf_iops, b.pf_out, hipHostMallocDefault);
+              b.pf_wom_p = b.pf_wom.p, b.pf_iops_p = b.pf_iops.p;
+            }
           } else if (j->kind == R0HIP_JOB_RV32IM_BACKS) {
             // the records were checked at submit; no index, offsets or values are staged
             const r0hip_raw_preflight_trace& pf = j->trace.preflight;
@@ -678,7 +759,7 @@ struct WorkerImpl {
             std::lock_guard<std::mutex> lk(b.mu);
             if (j->error) throw std::runtime_error(j->error);
           }
-          seal = prove_recursion_program_input(job_program(j), nullptr, 0, b.pf_wom.p, b.pf_iops.p, nullptr,
+          seal = prove_recursion_program_input(job_program(j), nullptr, 0, b.pf_wom_p, b.pf_iops_p, nullptr,
                                                keyed_noise(key, j->ticket), &mix);
         } else if (j->kind == R0HIP_JOB_RV32IM_BACKS) {
           // the set's counts and BigInt records were written by the uploader before the hand-over
@@ -706,6 +787,11 @@ struct WorkerImpl {
         drain_after_error();  // kernels queued before the throw may still read this set
       }
       b.wait_landed();  // the uploader is done with this job before the set is refilled
+      if (b.pf_slot >= 0) {
+        // the stream has drained on both paths above: nothing reads the slot's buffers any more
+        pool.release(b.pf_slot);
+        b.pf_slot = -1;
+      }
       free_q.put(s);
       if (ok && verify) to_verifier(j, std::move(seal));
       else finish(j);
@@ -761,6 +847,7 @@ struct WorkerImpl {
       to_verifier(nullptr, {});
       verifier.join();
     }
+    pool.stop();  // idle: every job was taken and every slot given back before the threads above ended
     for (auto& b : sets)
       if (b.ev) (void)hipEventDestroy(b.ev);
     sets.clear();
@@ -1111,6 +1198,8 @@ extern "C" const char* r0hip_worker_submit(r0hip_worker* w, r0hip_worker_job* jo
       m.outstanding++;
       m.fifo.emplace_back(job, info);
       if (m.witness_check) m.checked_jobs.insert(job);
+      // with a preflight pool a kind-4 job goes to its queue too, in the same (ticket) order
+      if (job->kind == R0HIP_JOB_RECURSION_INPUT && m.pool.push(job)) m.pooled_jobs.insert(job);
     }
     m.cv_in.notify_one();
   });
@@ -1121,6 +1210,51 @@ extern "C" const char* r0hip_worker_set_witness_check(r0hip_worker* w, int on) {
     R0_REQUIRE(w, "r0hip_worker_set_witness_check: w is NULL");
     std::lock_guard<std::mutex> lk(w->impl.mu);
     w->impl.witness_check = on != 0;
+  });
+}
+
+extern "C" const char* r0hip_worker_set_preflight_threads(r0hip_worker* w, uint32_t n, uint32_t* was) {
+  return guarded([&] {
+    R0_REQUIRE(w, "r0hip_worker_set_preflight_threads: w is NULL");
+    R0_REQUIRE(n <= 8, "r0hip_worker_set_preflight_threads: n " + std::to_string(n) + " above 8");
+    WorkerImpl& m = w->impl;
+    // under mu to the end: no submit between the check and the new pool
+    std::lock_guard<std::mutex> lk(m.mu);
+    R0_REQUIRE(!m.stopping, "r0hip_worker_set_preflight_threads: the worker is shutting down");
+    R0_REQUIRE(m.outstanding == 0, "r0hip_worker_set_preflight_threads: n " + std::to_string(n) + " refused with " +
+                                       std::to_string(m.outstanding) + " jobs outstanding");
+    // nothing outstanding: the pool's queue is empty and every slot is back, so its threads only wait
+    const uint32_t now = m.pool.threads();
+    if (n != now) m.pool.resize(n, uint32_t(m.k));
+    if (was) *was = now;
+  });
+}
+
+extern "C" const char* r0hip_worker_get_stats(r0hip_worker* w, r0hip_worker_stats* out, size_t out_size) {
+  return guarded([&] {
+    R0_REQUIRE(w, "r0hip_worker_get_stats: w is NULL");
+    R0_REQUIRE(out, "r0hip_worker_get_stats: out is NULL");
+    R0_REQUIRE(out_size == sizeof(r0hip_worker_stats), "r0hip_worker_get_stats: out_size " + std::to_string(out_size) +
+                                                           " is not sizeof(r0hip_worker_stats) " +
+                                                           std::to_string(sizeof(r0hip_worker_stats)));
+    WorkerImpl& m = w->impl;
+    r0hip_worker_stats st{};
+    uint64_t bytes = 0;
+    const PreflightPoolStats ps =
+        m.pool.stats([&](const PfSlot& s) { bytes += s.bytes.load(std::memory_order_relaxed); });
+    st.preflight_threads = ps.threads;
+    st.preflight_slots = ps.slots;
+    st.peak_slots_in_use = ps.peak_slots_in_use;
+    st.pool_jobs = ps.jobs;
+    st.slot_bytes = bytes;
+    st.pool_busy_ms = ps.busy_ms;
+    {
+      std::lock_guard<std::mutex> lk(m.stats_mu);
+      st.inline_jobs = m.inline_jobs;
+      st.uploader_preflight_ms = m.uploader_preflight_ms;
+      st.uploader_wait_preflight_ms = m.uploader_wait_preflight_ms;
+    }
+    *out = st;
   });
 }
 

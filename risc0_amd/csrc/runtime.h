@@ -431,6 +431,9 @@ struct RecursionInputCounts {
   size_t n_wom, n_iops, n_output;
 };
 RecursionInputCounts recursion_program_prepare_input(const r0hip_recursion_program* h);
+// the same counts when the plan exists already, without touching the device (any thread); false:
+// the handle has no plan yet and only recursion_program_prepare_input can make it
+bool recursion_program_planned_counts(const r0hip_recursion_program* h, RecursionInputCounts* out);
 void recursion_program_preflight_into(const r0hip_recursion_program* h, const uint32_t* h_input, size_t n_input,
                                       uint32_t* wom, uint32_t* iops, uint32_t* output);
 std::vector<uint32_t> prove_recursion_program_input(const r0hip_recursion_program* h, const uint32_t* h_input,

@@ -139,6 +139,8 @@ def _declare(L):
         "r0hip_worker_submit": [vp, vp],
         "r0hip_worker_wait": [vp, C.POINTER(vp), C.c_int64],
         "r0hip_worker_destroy": [vp],
+        "r0hip_worker_set_preflight_threads": [vp, C.c_uint32, C.POINTER(C.c_uint32)],
+        "r0hip_worker_get_stats": [vp, vp, sz],
         "r0hip_rv32im_bigint_accum_inject": [vp, sz, u32p, vp, sz],
         "r0hip_last_profile": [C.c_char_p, sz],
         "r0hip_set_kernel_timing": [C.c_int],
@@ -1121,6 +1123,14 @@ class WorkerInputJobStruct(C.Structure):
                 ("h_output", C.c_void_p), ("output_cap", C.c_size_t), ("n_output", C.c_size_t)]
 
 
+class WorkerStats(C.Structure):
+    """struct r0hip_worker_stats (include/r0hip.h): which way the worker's kind-4 preflights went"""
+    _fields_ = [("preflight_threads", C.c_uint32), ("preflight_slots", C.c_uint32),
+                ("peak_slots_in_use", C.c_uint32), ("reserved", C.c_uint32), ("pool_jobs", C.c_uint64),
+                ("inline_jobs", C.c_uint64), ("slot_bytes", C.c_uint64), ("pool_busy_ms", C.c_double),
+                ("uploader_preflight_ms", C.c_double), ("uploader_wait_preflight_ms", C.c_double)]
+
+
 JOB_RV32IM_TRACE, JOB_RECURSION, JOB_RV32IM_BACKS, JOB_RECURSION_PROGRAM, JOB_RECURSION_INPUT = 0, 1, 2, 3, 4
 
 
@@ -1206,6 +1216,21 @@ class Worker:
         set_witness_check checks a proof; a violated job fails alone with the check's message"""
         check(lib().r0hip_worker_set_witness_check(self._handle(), 1 if on else 0))
 
+    def set_preflight_threads(self, n):
+        """r0hip_worker_set_preflight_threads: kind-4 preflights on n pool threads (1..8) ahead of
+        the uploader, or on the uploader thread itself (0, the default). Refused (R0HipError) above
+        8 and while a job is outstanding. Returns the previous n."""
+        was = C.c_uint32()
+        check(lib().r0hip_worker_set_preflight_threads(self._handle(), n, C.byref(was)))
+        return int(was.value)
+
+    def stats(self):
+        """r0hip_worker_get_stats as a WorkerStats: pool_jobs and inline_jobs tell which thread ran
+        each kind-4 preflight, uploader_wait_preflight_ms whether the uploader still waits"""
+        st = WorkerStats()
+        check(lib().r0hip_worker_get_stats(self._handle(), C.byref(st), C.sizeof(st)))
+        return st
+
     def _submit(self, job, mix_words, keep):
         seal = np.zeros(self.seal_cap, dtype=np.uint32)
         mix = np.zeros(mix_words, dtype=np.uint32)
@@ -1278,19 +1303,24 @@ class Worker:
                                        roots.ctypes.data if roots.size else None, roots.size // 8)
         return self._submit(job, 20, (pj, program, w, c, i, roots))
 
-    def submit_recursion_input(self, program, inp, code_roots=None, po2=None, suite=None):
+    def submit_recursion_input(self, program, inp, code_roots=None, po2=None, suite=None, prepare=True,
+                               output_cap=None):
         """queue one recursion proof from a RecursionProgram and the reference's `input` (kind
-        R0HIP_JOB_RECURSION_INPUT): the preflight runs on the worker's uploader thread. Returns
-        its ticket; output(ticket) gives Preflight.output once wait() has returned the job."""
+        R0HIP_JOB_RECURSION_INPUT): the preflight runs on the worker's uploader thread, or on a
+        pool thread after set_preflight_threads. Returns its ticket; output(ticket) gives
+        Preflight.output once wait() has returned the job. prepare=False leaves a program without
+        a plan as it is (the worker makes the plan; the output buffer then needs output_cap, its
+        size in words, which also overrides the prepared program's own count)."""
         x = np.ascontiguousarray(inp, dtype=np.uint32).reshape(-1)
         roots = np.ascontiguousarray(np.zeros(0, np.uint32) if code_roots is None else code_roots,
                                      dtype=np.uint32).reshape(-1)
         if roots.size % 8:
             raise R0HipError("code_roots holds 8 words per root")
         p_suite, p_po2 = program.info()[:2]
-        if not program.input_info().prepared:
+        if prepare and not program.input_info().prepared:
             program.prepare_input()
-        out = np.zeros(program.input_info().n_output + 1, dtype=np.uint32)
+        cap = program.input_info().n_output if output_cap is None else int(output_cap)
+        out = np.zeros(cap + 1, dtype=np.uint32)
         ij = WorkerInputJobStruct()
         ij.program = program._handle().value
         ij.h_input, ij.n_input = x.ctypes.data if x.size else None, x.size

@@ -32,6 +32,22 @@ when the median gain exceeds that spread. All seals of a round must be equal. On
 (default profiles/recursion_input_ab.json) and the same line on stdout.
 
     python3 tools/bench_recursion_input.py [--po2 18] [--repeats 7] [--warmups 2] [--jobs 12] [--inflight 3]
+
+--pool-ab: the worker's preflight pool (r0hip_worker_set_preflight_threads) instead of the legs above,
+into profiles/worker_preflight_pool_ab.json. Per repeat, alternated: kind 3 (the floor: arrays prepared
+outside) and kind 4 with n = 0, 1, 2 and 3 pool threads, --jobs jobs at --inflight in flight, ms per job,
+with the worker's own counters (r0hip_worker_get_stats) per leg; then a mixed queue that alternates kind-4
+jobs with the rv32im jobs of tests/rv32im_trace.ecall_trace(--ecall-po2, reps=--ecall-reps) that
+tools/bench_backs.py uses, at n = 0 and at every n > 0. With --parent-lib PATH (a libr0hip.so built from
+the parent commit, under the git-ignored risc0_amd/lib_variants/) the kind-4 leg is first run on that
+library in a child process of the same session (R0HIP_LIB; one process holds one library), with the same
+program, warm-ups and repeats; the n = 0 leg must lie within that leg's spread. Item 9's rule per pool
+size: faster only when the median gain over the compared leg exceeds that leg's spread.
+
+--p2-share: no GPU. Builds tools/micro/preflight_p2_share.cpp with g++ -O3 and runs it on the same
+program: the preflight alone (rpf::run), the program's Poseidon2 permutations alone (poseidon2_mix on a
+chained state, as many as the program has p2_partial rows), and r0hip_recursion_preflight from Python
+for the same program; prints one JSON line (and writes --out if given).
 """
 import argparse
 import ctypes as C
@@ -57,8 +73,17 @@ def parse():
     ap.add_argument("--inflight", type=int, default=3)
     ap.add_argument("--suite", default="poseidon2")
     ap.add_argument("--wait-s", type=float, default=300.0)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "recursion_input_ab.json"))
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--pool-ab", action="store_true")
+    ap.add_argument("--p2-share", action="store_true")
+    ap.add_argument("--parent-lib", default=None)
+    ap.add_argument("--ecall-po2", type=int, default=16)
+    ap.add_argument("--ecall-reps", type=int, default=30)
+    ap.add_argument("--pool-child", default=None, help=argparse.SUPPRESS)  # the parent-library leg: an .npz
     args = ap.parse_args()
+    if args.out is None and not args.p2_share:
+        args.out = os.path.join(ROOT, "profiles",
+                                "worker_preflight_pool_ab.json" if args.pool_ab else "recursion_input_ab.json")
     if args.repeats < 5:
         ap.error("--repeats must be at least 5")
     return args
@@ -89,8 +114,227 @@ def witgen_kernels(r, hal, fn):
     return {k: round(v[0], 3) for k, v in times.items() if k.startswith("recursion_witgen")}
 
 
+def build_program(np, po2):
+    import recursion_program as RP
+    t0 = time.perf_counter()
+    prog_rows, inp = RP.random_program(np.random.default_rng(SEED), (1 << po2) - RP.ZK_CYCLES - 1)
+    code = np.ascontiguousarray(prog_rows.encoded(), dtype=np.uint32).reshape(-1)
+    print(f"one po2={po2} program of {len(prog_rows.rows)} rows built in {time.perf_counter() - t0:.1f} s",
+          file=sys.stderr, flush=True)
+    return code, np.array(inp, dtype=np.uint32), len(prog_rows.rows)
+
+
+def worker_run(r, hal, args, po2, n, submit, jobs):
+    """one fresh worker with n pool threads: submit(w, i) for i < jobs, wait for all; returns ms per
+    job, the seals by ticket and the worker's counters (None on a library without them)"""
+    with r.Worker(hal, max_po2=po2, in_flight=args.inflight, verify=True, noise_key=KEY) as w:
+        if n:
+            w.set_preflight_threads(n)
+        hal.synchronize()
+        t = time.perf_counter()
+        for i in range(jobs):
+            submit(w, i)
+        seals = {}
+        for _ in range(jobs):
+            res = w.wait(args.wait_s)
+            if res is None:
+                raise SystemExit("bench_recursion_input: a worker job did not come back")
+            if res[3] is not None:
+                raise SystemExit(f"bench_recursion_input: job {res[0]}: {res[3]}")
+            seals[res[0]] = res[1]
+        per_job = 1000.0 * (time.perf_counter() - t) / jobs
+        st = None
+        if hasattr(r.lib(), "r0hip_worker_get_stats"):
+            s = w.stats()
+            st = {"pool_jobs": int(s.pool_jobs), "inline_jobs": int(s.inline_jobs),
+                  "peak_slots_in_use": int(s.peak_slots_in_use), "preflight_slots": int(s.preflight_slots),
+                  "slot_bytes": int(s.slot_bytes), "pool_busy_ms": round(s.pool_busy_ms, 3),
+                  "uploader_preflight_ms": round(s.uploader_preflight_ms, 3),
+                  "uploader_wait_preflight_ms": round(s.uploader_wait_preflight_ms, 3)}
+    return per_job, seals, st
+
+
+def pool_child(args):
+    """the kind-4 leg on whatever library R0HIP_LIB names (the parent's): one JSON line"""
+    import numpy as np
+    import risc0_amd as r
+    z = np.load(args.pool_child)
+    code, inp, po2 = z["code"], z["inp"], args.po2
+    hal = r.HipHal(args.suite)
+    prog = r.RecursionProgram.create(hal, po2, code)
+    prog.prepare_input()
+    ms = []
+    for rep in range(args.warmups + args.repeats):
+        m, _seals, _st = worker_run(r, hal, args, po2, 0, lambda w, i: w.submit_recursion_input(prog, inp), args.jobs)
+        if rep >= args.warmups:
+            ms.append(m)
+    prog.close()
+    print(json.dumps({"library": os.environ.get("R0HIP_LIB"), "has_pool": hasattr(r.lib(), "r0hip_worker_get_stats"),
+                      **summary(ms)}))
+
+
+def median_stats(stats):
+    """the per-repeat counters of one leg as their medians"""
+    return {k: round(statistics.median(s[k] for s in stats), 3) for k in stats[0]} if stats and stats[0] else None
+
+
+def pool_ab(args):
+    import subprocess
+    import tempfile
+
+    import numpy as np
+    import risc0_amd as r
+    import rv32im_trace as T
+
+    po2 = args.po2
+    code, inp, code_rows = build_program(np, po2)
+    wom, cyc, iops, _output = r.recursion_preflight(code, po2, inp)
+    out = {}
+    if args.parent_lib:
+        # before this process opens the GPU: one process, one library
+        with tempfile.TemporaryDirectory() as d:
+            npz = os.path.join(d, "program.npz")
+            np.savez(npz, code=code, inp=inp)
+            cmd = [sys.executable, os.path.abspath(__file__), "--pool-child", npz, "--po2", str(po2), "--repeats",
+                   str(args.repeats), "--warmups", str(args.warmups), "--jobs", str(args.jobs), "--inflight",
+                   str(args.inflight), "--suite", args.suite, "--wait-s", str(args.wait_s)]
+            env = dict(os.environ, R0HIP_LIB=os.path.abspath(args.parent_lib))
+            child = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=1200)
+            if child.returncode:
+                raise SystemExit("bench_recursion_input: the parent-library leg failed:\n" + child.stderr[-3000:])
+            out["parent_kind4"] = json.loads(child.stdout.strip().split("\n")[-1])
+            if out["parent_kind4"].pop("has_pool"):
+                raise SystemExit("bench_recursion_input: --parent-lib has the pool's entry points: not the parent")
+        print(f"parent kind 4: {out['parent_kind4']['ms']} ms per job", file=sys.stderr, flush=True)
+
+    hal = r.HipHal(args.suite)
+    prog = r.RecursionProgram.create(hal, po2, code)
+    prog.prepare_input()
+    te = T.ecall_trace(args.ecall_po2, seed=3, bigint=True, reps=args.ecall_reps)
+    tcyc, ttx = te.arrays()
+    ecall = r.TraceJob(*(r.pinned_copy(a) for a in (te.global_words(), *te.injector_arrays(), tcyc, ttx)),
+                       te.table_split_cycle, bigint=te.bigint_array(), bigint_records=te.bigint_records())
+    sizes = [0, 1, 2, 3]
+
+    def kind3(w, i):
+        w.submit_recursion_program(prog, wom, cyc, iops)
+
+    def kind4(w, i):
+        w.submit_recursion_input(prog, inp)
+
+    def mixed(w, i):
+        if i % 2:
+            w.submit_trace(ecall, args.ecall_po2)
+        else:
+            w.submit_recursion_input(prog, inp)
+
+    max_po2 = max(po2, args.ecall_po2)
+    legs = [("kind3", 0, kind3)] + [(f"kind4_n{n}", n, kind4) for n in sizes] + [(f"mixed_n{n}", n, mixed) for n in sizes]
+    ms, stats = {name: [] for name, _, _ in legs}, {name: [] for name, _, _ in legs}
+    equal = True
+    for rep in range(args.warmups + args.repeats):
+        seals = {}
+        for name, n, submit in legs:
+            m, seals[name], st = worker_run(r, hal, args, max_po2 if name.startswith("mixed") else po2, n, submit,
+                                            args.jobs)
+            if rep >= args.warmups:
+                ms[name].append(m)
+                stats[name].append(st)
+        for n in sizes:  # a seal depends on the job and its ticket alone
+            equal = equal and all(np.array_equal(seals["kind3"][k], seals[f"kind4_n{n}"][k]) for k in seals["kind3"])
+            equal = equal and all(np.array_equal(seals["mixed_n0"][k], seals[f"mixed_n{n}"][k]) for k in seals["mixed_n0"])
+    prog.close()
+    for name, _, _ in legs:
+        out[name] = summary(ms[name])
+        if name != "kind3":
+            out[name]["stats_median"] = median_stats(stats[name])
+        print(f"{name}: {out[name]['ms']} ms per job", file=sys.stderr, flush=True)
+    if args.parent_lib:
+        out["n0_vs_parent"] = compare(out, "parent_kind4", "kind4_n0")
+        out["n0_within_parent_spread"] = bool(abs(out["n0_vs_parent"]["gain_ms"]) <= out["n0_vs_parent"]["spread_ms"])
+    for n in sizes[1:]:
+        out[f"kind4_n{n}_vs_n0"] = compare(out, "kind4_n0", f"kind4_n{n}")
+        out[f"mixed_n{n}_vs_n0"] = compare(out, "mixed_n0", f"mixed_n{n}")
+        out[f"kind4_n{n}_vs_kind3"] = compare(out, "kind3", f"kind4_n{n}")
+    best = min(sizes[1:], key=lambda n: out[f"mixed_n{n}"]["median"])
+    out["mixed_best_n"] = best
+
+    buf, total = C.create_string_buffer(256), C.c_uint64(0)
+    r.check(r.lib().r0hip_device_info(buf, 256, C.byref(total)))
+    result = {
+        "what": "the worker's kind-4 jobs (a resident program and its input words) with the preflight on the "
+                "uploader thread (n0) and on a pool of n host threads (r0hip_worker_set_preflight_threads), kind 3 "
+                "(arrays prepared outside) as the floor; mixed_*: kind-4 jobs alternating with rv32im ecall_trace "
+                "jobs in one queue. ms per job = host clock from the first submit to the last wait / jobs, a fresh "
+                "worker per run, made before the timed region. Legs alternated in one process after warm-up rounds; "
+                "parent_kind4: the kind-4 leg on a library built from the parent commit, in a child process of the "
+                "same session before the other legs. stats_median: r0hip_worker_get_stats after the last job, median "
+                "over the repeats. Not measured: a real lift or join program, other suites, other in_flight, a "
+                "loaded host",
+        "device": buf.value.decode(), "suite": args.suite, "po2": po2, "repeats": args.repeats,
+        "warmup_rounds": args.warmups, "worker_jobs": args.jobs, "worker_in_flight": args.inflight,
+        "code_rows": code_rows, "input_words": int(inp.size), "ecall_po2": args.ecall_po2,
+        "ecall_reps": args.ecall_reps, "host_cpus": len(os.sched_getaffinity(0)), **out, "seals_equal": bool(equal),
+    }
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as fh:
+        fh.write(json.dumps(result, indent=1) + "\n")
+    print(json.dumps(result))
+    if not equal:
+        print("bench_recursion_input: the legs' seals differ", file=sys.stderr)
+        sys.exit(1)
+
+
+def p2_share(args):
+    import platform
+    import subprocess
+    import tempfile
+
+    import numpy as np
+    import risc0_amd as r
+
+    po2 = args.po2
+    code, inp, code_rows = build_program(np, po2)
+    py_ms = []
+    for _ in range(args.warmups + args.repeats):
+        t = time.perf_counter()
+        r.recursion_preflight(code, po2, inp)
+        py_ms.append(1000.0 * (time.perf_counter() - t))
+    with tempfile.TemporaryDirectory() as d:
+        exe, case = os.path.join(d, "preflight_p2_share"), os.path.join(d, "case.bin")
+        csrc = os.path.join(ROOT, "risc0_amd", "csrc")
+        subprocess.run(["g++", "-O3", "-std=c++17", "-I", csrc, "-o", exe,
+                        os.path.join(ROOT, "tools", "micro", "preflight_p2_share.cpp"),
+                        os.path.join(csrc, "recursion_preflight.cpp")], check=True)
+        np.concatenate([np.array([po2, code.size, inp.size], np.uint32), code, inp]).tofile(case)
+        native = json.loads(subprocess.run([exe, case, str(args.warmups), str(args.repeats)], capture_output=True,
+                                           text=True, check=True).stdout)
+    cpu = ""
+    try:
+        cpu = [ln.split(":", 1)[1].strip() for ln in open("/proc/cpuinfo") if ln.startswith("model name")][0]
+    except (OSError, IndexError):
+        cpu = platform.processor()
+    result = {"what": "the host preflight of one program and the share of its Poseidon2 permutations, one thread, "
+                      "no GPU: preflight = rpf::run alone (decoded program), permutations = as many poseidon2_mix "
+                      "calls on a chained 24-word state as the program has p2_partial rows, c_abi = "
+                      "r0hip_recursion_preflight from Python (decode, run, the copies out)",
+              "cpu": cpu, "po2": po2, "code_rows": code_rows, "repeats": args.repeats, "warmup_rounds": args.warmups,
+              **native, "c_abi": summary(py_ms[args.warmups:])}
+    result["p2_share_of_preflight"] = round(result["permutations"]["median"] / result["preflight"]["median"], 4)
+    if args.out:
+        with open(args.out, "w") as fh:
+            fh.write(json.dumps(result, indent=1) + "\n")
+    print(json.dumps(result))
+
+
 def main():
     args = parse()
+    if args.pool_child:
+        return pool_child(args)
+    if args.pool_ab:
+        return pool_ab(args)
+    if args.p2_share:
+        return p2_share(args)
     import numpy as np
     import recursion_program as RP
     import risc0_amd as r
