@@ -1021,6 +1021,93 @@ const char* r0hip_constraint_rows(const char* circuit, uint32_t po2, const uint3
 const char* r0hip_constraint_term(const char* circuit, const uint32_t* h_taps, const uint32_t* h_mix,
                                   const uint32_t* h_global, const uint32_t* h_poly_mix, int32_t* term);
 
+/* ---- circuits compiled in: the shipped ones, the demo circuit, build-time plug-ins ----
+ * The circuit-generic entry points (r0hip_eval_check, r0hip_poly_ext, r0hip_constraint_rows,
+ * r0hip_constraint_term, r0hip_prove_segment, r0hip_prove_segment_cb, r0hip_prove_segments,
+ * r0hip_verify_seal*, the testing variants) take any name the library was built with: "rv32im",
+ * "recursion", "demo", and every circuit of the directories given to the build as
+ * EXTRA_CIRCUIT_DIRS ("Adding a circuit / checking a card"). An unknown name's
+ * error lists the names compiled in. The rv32im version word and the two device accumulations
+ * (r0hip_prove_segment_accum) stay tied to their circuits' names.
+ * r0hip_circuit_info: what a caller needs to size a circuit's buffers. circuit = NULL: the names,
+ * space-separated in build order, into names (names_cap bytes, NUL-terminated; too small is an
+ * error); out is not written. Otherwise *out (out_size = sizeof(r0hip_circuit_desc)) describes the
+ * named circuit and names, if given, receives its name. Host-only. */
+typedef struct r0hip_circuit_desc {
+  uint32_t group_sizes[3]; /* columns of accum, code, data */
+  uint32_t mix_size;       /* words drawn after the data commit */
+  uint32_t output_size;    /* words of the global (output) buffer */
+  uint32_t n_taps;         /* taps, the length of r0hip_poly_ext's h_eval_u in FpExt */
+  uint8_t info[16];        /* the circuit's CircuitInfo bytes */
+} r0hip_circuit_desc;
+/* [host-only] */
+const char* r0hip_circuit_info(const char* circuit, r0hip_circuit_desc* out, size_t out_size, char* names,
+                               size_t names_cap);
+
+/* r0hip_prove_segment with the accum group made after the mix is drawn, for a circuit whose
+ * accumulation the library does not have. The library commits code and data, draws the
+ * circuit's mix_size words, allocates d_accum (2^po2 x group_sizes[0] words, filled with
+ * 0xFFFFFFFF), drains its stream and calls accum(user, h_mix, d_accum, stream) on the calling
+ * thread; then it zeroizes the group, runs the witness check if that mode is on, commits the
+ * group and finishes the proof. The function may queue work on stream (a hipStream_t, the
+ * calling thread's) or write d_accum through synchronous copies of its own, the r0hip_memcpy_*
+ * and per-op entry points included; it must not prove or verify on this thread. It returns NULL,
+ * or a message: the call then fails with "accum callback: <message>" (the string stays the
+ * callback's; the library copies it). d_accum is the library's and is gone after the call. For
+ * rv32im and recursion a callback that copies in the group r0hip_prove_segment was given yields
+ * that call's seal, word for word. Proof streams, deferred mode and the memory hand-back are
+ * r0hip_prove_segment's. h_mix_out (may be NULL): the mix words. */
+typedef const char* (*r0hip_accum_fn)(void* user, const uint32_t* h_mix, uint32_t* d_accum, void* stream);
+/* [drains] */
+const char* r0hip_prove_segment_cb(const char* circuit, int suite, uint32_t po2, const uint32_t* d_code,
+                                   const uint32_t* d_data, r0hip_accum_fn accum, void* user, uint32_t* d_global,
+                                   int write_version, uint32_t version, uint32_t* h_seal, size_t seal_cap,
+                                   size_t* seal_len, uint32_t* h_mix_out);
+
+/* ---- the demo circuit and the card self-test ----
+ * "demo" (risc0_amd/circuits/demo.*, written by tools/gen_demo_circuit.py) is a small circuit of
+ * this library's own whose valid witness the library can make: code = the selectors first, on,
+ * last; data = a, b, s with (a, b)[i] = (b, a + b)[i - 1] and s = a * b on the n_active rows;
+ * accum = one FpExt, the running sum of m * a with m the four mix words; global = a[0], b[0],
+ * b[n_active - 1]. Every constraint carries a selector that is 0 above n_active, so those rows
+ * of data and accum may hold anything (ZK noise).
+ * r0hip_demo_witness: d_code (3 columns x 2^po2 rows, every row) and d_global (3 words) are
+ * written; of d_data (3 columns) only the rows below n_active: fill the group with noise first
+ * (r0hip_fill_chacha20). a0, b0: Montgomery words below p. 1 <= n_active <= 2^po2, po2 2..24.
+ * r0hip_demo_accum: the rows below n_active of d_accum (4 columns) from d_data's column a and
+ * h_mix (4 Montgomery words); what an r0hip_prove_segment_cb callback for "demo" queues. */
+/* [queues] */
+const char* r0hip_demo_witness(uint32_t po2, size_t n_active, uint32_t a0, uint32_t b0, uint32_t* d_code,
+                               uint32_t* d_data, uint32_t* d_global);
+/* [queues] */
+const char* r0hip_demo_accum(uint32_t po2, size_t n_active, const uint32_t* d_data, const uint32_t* h_mix,
+                             uint32_t* d_accum);
+
+/* r0hip_selftest: a health check of the card this thread is on, before it takes jobs. For every
+ * hash suite in suites_mask (bit R0HIP_POSEIDON2, R0HIP_SHA256, R0HIP_POSEIDON254), at 2^po2 rows:
+ *   a  the demo witness is made on the device, proved through r0hip_prove_segment_cb and the seal
+ *      checked by r0hip_verify_seal (validity equation included) and again with the openings on
+ *      the device (R0HIP_VERIFY_DEVICE);
+ *   b  r0hip_constraint_rows finds no bad row in that witness, and exactly the two rows that tap
+ *      it after one word of column a is changed in a copy;
+ *   c  the seal with one word changed is rejected by the verifier.
+ * Every negative case is a verdict of a check, never a device fault. The report (out_size =
+ * sizeof(r0hip_selftest_report)) has, per suite, the checks that passed (bit 0 a, 1 b, 2 c), the
+ * milliseconds of each and the seal's length in words; suites not asked for are zero. Returns
+ * NULL only when every check of every suite asked for passed, else a message naming the first
+ * that did not. Refused on the host: a mask of 0 or above 7, po2 outside 8..24, a NULL report,
+ * an out_size that is not the struct's. The thread keeps no device memory afterwards. */
+typedef struct r0hip_selftest_suite {
+  uint32_t passed;   /* bit 0: a, bit 1: b, bit 2: c */
+  uint32_t seal_len; /* words of the seal of check a */
+  double ms[3];      /* wall time of a, b, c */
+} r0hip_selftest_suite;
+typedef struct r0hip_selftest_report {
+  r0hip_selftest_suite suite[3]; /* by suite id */
+} r0hip_selftest_report;
+/* [drains] */
+const char* r0hip_selftest(uint32_t suites_mask, uint32_t po2, r0hip_selftest_report* out, size_t out_size);
+
 /* kernel-level timing with HIP events on the library stream: enable, run, then read
  * "name=total_ms:calls:alg_bytes;..." (alg_bytes = algorithmic HBM bytes) */
 /* [drains] */

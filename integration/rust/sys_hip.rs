@@ -37,6 +37,33 @@ pub struct R0HipConstraintReport {
     pub rows: [u32; 16],
 }
 
+/// struct r0hip_circuit_desc: the sizes of a circuit compiled into the library.
+#[repr(C)]
+pub struct R0HipCircuitDesc {
+    pub group_sizes: [u32; 3],
+    pub mix_size: u32,
+    pub output_size: u32,
+    pub n_taps: u32,
+    pub info: [u8; 16],
+}
+
+/// r0hip_accum_fn: fills the accum group once the mix is known; NULL, or a message that fails the proof.
+pub type R0HipAccumFn = Option<
+    unsafe extern "C" fn(user: *mut c_void, h_mix: *const u32, d_accum: *mut u32, stream: *mut c_void) -> *const c_char,
+>;
+
+/// struct r0hip_selftest_suite / r0hip_selftest_report: what r0hip_selftest found, per hash suite.
+#[repr(C)]
+pub struct R0HipSelftestSuite {
+    pub passed: u32,
+    pub seal_len: u32,
+    pub ms: [f64; 3],
+}
+#[repr(C)]
+pub struct R0HipSelftestReport {
+    pub suite: [R0HipSelftestSuite; 3],
+}
+
 #[repr(C)]
 pub struct R0HipBigIntBack {
     pub row: u32,
@@ -780,6 +807,53 @@ unsafe extern "C" {
         h_global: *const u32,
         h_poly_mix: *const u32,
         term: *mut i32,
+    ) -> *const c_char;
+
+    // ---- circuits compiled in, accumulation by callback, the demo circuit, the self-test ----
+    pub fn r0hip_circuit_info(
+        circuit: *const c_char,
+        out: *mut R0HipCircuitDesc,
+        out_size: usize,
+        names: *mut c_char,
+        names_cap: usize,
+    ) -> *const c_char;
+    pub fn r0hip_prove_segment_cb(
+        circuit: *const c_char,
+        suite: c_int,
+        po2: u32,
+        d_code: *const u32,
+        d_data: *const u32,
+        accum: R0HipAccumFn,
+        user: *mut c_void,
+        d_global: *mut u32,
+        write_version: c_int,
+        version: u32,
+        h_seal: *mut u32,
+        seal_cap: usize,
+        seal_len: *mut usize,
+        h_mix_out: *mut u32,
+    ) -> *const c_char;
+    pub fn r0hip_demo_witness(
+        po2: u32,
+        n_active: usize,
+        a0: u32,
+        b0: u32,
+        d_code: *mut u32,
+        d_data: *mut u32,
+        d_global: *mut u32,
+    ) -> *const c_char;
+    pub fn r0hip_demo_accum(
+        po2: u32,
+        n_active: usize,
+        d_data: *const u32,
+        h_mix: *const u32,
+        d_accum: *mut u32,
+    ) -> *const c_char;
+    pub fn r0hip_selftest(
+        suites_mask: u32,
+        po2: u32,
+        out: *mut R0HipSelftestReport,
+        out_size: usize,
     ) -> *const c_char;
 
     // ---- diagnostics (scope! spans and the MemoryTracker) ----

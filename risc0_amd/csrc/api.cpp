@@ -25,6 +25,7 @@
 #include "backs.h"
 #include "circuit.h"
 #include "devmem.h"
+#include "plugin.h"
 #include "recursion_preflight.h"
 #include "runtime.h"
 #include "rv32im_witgen.h"
@@ -40,6 +41,9 @@ std::vector<uint32_t> prove_segment(const CircuitDef& c, int suite, uint32_t po2
                                     bool write_version, uint32_t version, std::vector<uint32_t>* mix_out,
                                     const UploadGate* uploads = nullptr, const AccumStep* acc = nullptr,
                                     GroupWork* code_early = nullptr, const CachedGroup* code_cached = nullptr);
+std::vector<uint32_t> prove_segment_cb(const CircuitDef& c, int suite, uint32_t po2, const uint32_t* code,
+                                       const uint32_t* data, uint32_t* global, bool write_version, uint32_t version,
+                                       std::vector<uint32_t>* mix_out, const AccumCallback& cb);
 GroupWork commit_group_side(int k, int suite, const uint32_t* witness, size_t cols, size_t po2);
 std::vector<uint32_t> commit_group_keep(hipStream_t s, int suite, uint32_t* coeffs, uint32_t* evaluated, uint32_t* nodes,
                                         const uint32_t* witness, size_t cols, size_t po2);
@@ -1220,7 +1224,7 @@ const char* r0hip_eval_check(const char* circuit, uint32_t* d_check, const uint3
                              uint32_t po2) {
   return wrap([&] {
     const CircuitDef* c = find_circuit(circuit ? circuit : "");
-    R0_REQUIRE(c, std::string("unknown circuit ") + (circuit ? circuit : "(null)"));
+    R0_REQUIRE(c, unknown_circuit(circuit));
     R0_REQUIRE(d_check && d_groups && h_poly_mix, "eval_check: null argument");
     for (int g = 0; g < 3; g++) R0_REQUIRE(d_groups[g], "eval_check: null register group");
     stage_reset();
@@ -1235,7 +1239,7 @@ const char* r0hip_constraint_rows(const char* circuit, uint32_t po2, const uint3
     // every refusal on the host, before any device call
     const std::string who = "r0hip_constraint_rows: ";
     const CircuitDef* c = find_circuit(circuit ? circuit : "");
-    R0_REQUIRE(c, who + "unknown circuit " + (circuit ? circuit : "(null)"));
+    R0_REQUIRE(c, who + unknown_circuit(circuit));
     R0_REQUIRE(po2 >= 2 && po2 <= 24, who + "po2 " + std::to_string(po2) + " out of range (2..24)");
     R0_REQUIRE(d_code, who + "d_code is NULL");
     R0_REQUIRE(d_data, who + "d_data is NULL");
@@ -1256,7 +1260,7 @@ const char* r0hip_prove_segment(const char* circuit, int suite, uint32_t po2, co
                                 size_t* seal_len, uint32_t* h_mix_out) {
   return wrap([&] {
     const CircuitDef* c = find_circuit(circuit ? circuit : "");
-    R0_REQUIRE(c, std::string("unknown circuit ") + (circuit ? circuit : "(null)"));
+    R0_REQUIRE(c, unknown_circuit(circuit));
     std::vector<uint32_t> mix;
     std::vector<uint32_t> seal = prove_segment(*c, suite, po2, d_code, d_data, d_accum, d_global, write_version != 0,
                                                version, &mix);
@@ -1276,7 +1280,7 @@ const char* r0hip_prove_segment_accum(const char* circuit, int suite, uint32_t p
                                       size_t* seal_len, uint32_t* h_mix_out) {
   return wrap([&] {
     const CircuitDef* c = find_circuit(circuit ? circuit : "");
-    R0_REQUIRE(c, std::string("unknown circuit ") + (circuit ? circuit : "(null)"));
+    R0_REQUIRE(c, unknown_circuit(circuit));
     R0_REQUIRE(n_bigint == 0 || h_bigint, "prove_segment_accum: h_bigint is NULL with n_bigint > 0");
     std::vector<uint32_t> mix;
     const AccumStep acc{d_accum, work_cycles, false, h_bigint, n_bigint};
@@ -1288,6 +1292,181 @@ const char* r0hip_prove_segment_accum(const char* circuit, int suite, uint32_t p
       R0_REQUIRE(seal.size() <= seal_cap, "seal buffer too small");
       memcpy(h_seal, seal.data(), seal.size() * 4);
     }
+  });
+}
+
+const char* r0hip_prove_segment_cb(const char* circuit, int suite, uint32_t po2, const uint32_t* d_code,
+                                   const uint32_t* d_data, r0hip_accum_fn accum, void* user, uint32_t* d_global,
+                                   int write_version, uint32_t version, uint32_t* h_seal, size_t seal_cap,
+                                   size_t* seal_len, uint32_t* h_mix_out) {
+  return wrap([&] {
+    const CircuitDef* c = find_circuit(circuit ? circuit : "");
+    R0_REQUIRE(c, unknown_circuit(circuit));
+    R0_REQUIRE(accum, "r0hip_prove_segment_cb: accum is NULL");
+    R0_REQUIRE(d_code && d_data && d_global, "r0hip_prove_segment_cb: null group");
+    std::vector<uint32_t> mix;
+    const AccumCallback cb{accum, user};
+    std::vector<uint32_t> seal =
+        prove_segment_cb(*c, suite, po2, d_code, d_data, d_global, write_version != 0, version, &mix, cb);
+    if (seal_len) *seal_len = seal.size();
+    if (h_mix_out) memcpy(h_mix_out, mix.data(), mix.size() * 4);
+    if (h_seal) {
+      R0_REQUIRE(seal.size() <= seal_cap, "seal buffer too small");
+      memcpy(h_seal, seal.data(), seal.size() * 4);
+    }
+  });
+}
+
+const char* r0hip_circuit_info(const char* circuit, r0hip_circuit_desc* out, size_t out_size, char* names,
+                               size_t names_cap) {
+  return wrap_nosync([&] {
+    std::string text;
+    if (!circuit) {
+      for (size_t i = 0; i < circuit_count(); i++) text += (i ? " " : "") + std::string(circuit_at(i).name);
+      R0_REQUIRE(names, "r0hip_circuit_info: names is NULL with no circuit named");
+    } else {
+      const CircuitDef* c = find_circuit(circuit);
+      R0_REQUIRE(c, "r0hip_circuit_info: " + unknown_circuit(circuit));
+      R0_REQUIRE(out, "r0hip_circuit_info: out is NULL");
+      R0_REQUIRE(out_size == sizeof(r0hip_circuit_desc),
+                 "r0hip_circuit_info: out_size " + std::to_string(out_size) + " is not sizeof(r0hip_circuit_desc) = " +
+                     std::to_string(sizeof(r0hip_circuit_desc)));
+      for (int g = 0; g < 3; g++) out->group_sizes[g] = uint32_t(c->group_size(g));
+      out->mix_size = uint32_t(c->mix_size);
+      out->output_size = uint32_t(c->output_size);
+      out->n_taps = uint32_t(c->n_taps);
+      memcpy(out->info, c->circuit_info, 16);
+      text = c->name;
+    }
+    if (names) {
+      R0_REQUIRE(text.size() < names_cap, "r0hip_circuit_info: names_cap " + std::to_string(names_cap) +
+                                              " is too small for " + std::to_string(text.size() + 1) + " bytes");
+      memcpy(names, text.c_str(), text.size() + 1);
+    }
+  });
+}
+
+const char* r0hip_demo_witness(uint32_t po2, size_t n_active, uint32_t a0, uint32_t b0, uint32_t* d_code,
+                               uint32_t* d_data, uint32_t* d_global) {
+  return wrap_dev([&] { demo_witness(stream(), po2, n_active, a0, b0, d_code, d_data, d_global); });
+}
+
+const char* r0hip_demo_accum(uint32_t po2, size_t n_active, const uint32_t* d_data, const uint32_t* h_mix,
+                             uint32_t* d_accum) {
+  return wrap_dev([&] { demo_accum(stream(), po2, n_active, d_data, h_mix, d_accum); });
+}
+
+}  // extern "C"
+
+namespace {
+// r0hip_selftest, one suite: the three checks, each timed; `why` names the first that failed
+struct DemoAccumArgs {
+  uint32_t po2;
+  size_t n;
+  const uint32_t* data;
+};
+const char* demo_accum_cb(void* user, const uint32_t* h_mix, uint32_t* d_accum, void* s) {
+  const DemoAccumArgs& a = *static_cast<const DemoAccumArgs*>(user);
+  demo_accum(static_cast<hipStream_t>(s), a.po2, a.n, a.data, h_mix, d_accum);  // a throw fails the proof as well
+  return nullptr;
+}
+// an error string of an extern "C" entry point as a std::string ("" = none), freed
+std::string take(const char* err) {
+  if (!err) return "";
+  std::string m = err;
+  free(const_cast<char*>(err));
+  return m;
+}
+void selftest_suite(const CircuitDef& c, int suite, uint32_t po2, r0hip_selftest_suite& rep, std::string& why) {
+  using clk = std::chrono::steady_clock;
+  auto ms_since = [](clk::time_point t0) { return std::chrono::duration<double, std::milli>(clk::now() - t0).count(); };
+  auto fail = [&](const std::string& m) {
+    if (why.empty()) why = "suite " + std::to_string(suite) + ": " + m;
+  };
+  hipStream_t s = stream();
+  const size_t rows = size_t(1) << po2, n = rows - rows / 8;  // the top eighth stands for the ZK rows
+  DevBuf code(3 * rows), data(3 * rows), global(3);
+  // a: witness, proof, both verifiers. The noise key is fixed: the run is the same every time.
+  auto t0 = clk::now();
+  ChaChaKey key{};
+  for (int i = 0; i < 8; i++) key.key[i] = 0x52304850u + uint32_t(i);
+  key.nonce[0] = uint32_t(suite);
+  fill_chacha20(s, data.p, 3 * rows, key);
+  demo_witness(s, po2, n, fp_encode(1), fp_encode(1), code.p, data.p, global.p);
+  DemoAccumArgs args{po2, n, data.p};
+  std::vector<uint32_t> mix;
+  std::vector<uint32_t> seal =
+      prove_segment_cb(c, suite, po2, code.p, data.p, global.p, false, 0, &mix, AccumCallback{demo_accum_cb, &args});
+  rep.seal_len = uint32_t(seal.size());
+  uint32_t got = 0;
+  std::string e = take(r0hip_verify_seal(c.name, suite, seal.data(), seal.size(), nullptr, 0, nullptr, &got));
+  if (e.empty() && got != po2) e = "the seal verifies at po2 " + std::to_string(got);
+  if (e.empty())
+    e = take(r0hip_verify_seal_on(R0HIP_VERIFY_DEVICE, c.name, suite, seal.data(), seal.size(), nullptr, 0, nullptr, &got));
+  if (e.empty()) rep.passed |= 1u;
+  else fail("a: the proof of the demo witness is not accepted: " + e);
+  rep.ms[0] = ms_since(t0);
+  // b: the rows check on the witness as proved, then with a[r] changed: rows r and r + 1 tap it
+  t0 = clk::now();
+  {
+    stage_reset();
+    DevBuf accum(4 * rows), dmix(4);
+    HIP_OK(hipMemsetD32Async(accum.p, 0xFFFFFFFFu, 4 * rows, s));
+    demo_accum(s, po2, n, data.p, mix.data(), accum.p);
+    eltwise_zeroize(s, accum.p, 4 * rows);
+    upload_async(dmix.p, mix.data(), 16);
+    const uint32_t* groups[3] = {accum.p, code.p, data.p};
+    const FpExt pm = constraint_rows_poly_mix(nullptr);
+    r0hip_constraint_report cr;
+    constraint_rows_run(c, po2, groups, dmix.p, global.p, mix.data(), nullptr, pm, nullptr, &cr);
+    bool ok = cr.bad_rows == 0;
+    if (!ok) fail("b: " + std::to_string(cr.bad_rows) + " rows of the demo witness violate a constraint, first " +
+                  std::to_string(cr.first_row));
+    const uint32_t r = uint32_t(n / 2);
+    uint32_t word = 0;
+    download(&word, data.p + r, 4);
+    word = fp_add(word, kOne);
+    upload(data.p + r, &word, 4);
+    constraint_rows_run(c, po2, groups, dmix.p, global.p, mix.data(), nullptr, pm, nullptr, &cr);
+    if (ok && !(cr.bad_rows == 2 && cr.n_rows == 2 && cr.rows[0] == r && cr.rows[1] == r + 1 && cr.first_row == r)) {
+      ok = false;
+      fail("b: a changed word in row " + std::to_string(r) + " is reported as " + std::to_string(cr.bad_rows) +
+           " bad rows, first " + std::to_string(cr.first_row));
+    }
+    if (ok) rep.passed |= 2u;
+  }
+  rep.ms[1] = ms_since(t0);
+  // c: one changed seal word is a rejection
+  t0 = clk::now();
+  if (!seal.empty()) {
+    seal[seal.size() / 2] ^= 1u;
+    e = take(r0hip_verify_seal(c.name, suite, seal.data(), seal.size(), nullptr, 0, nullptr, &got));
+    if (!e.empty()) rep.passed |= 4u;
+    else fail("c: the verifier accepts a seal with word " + std::to_string(seal.size() / 2) + " changed");
+  }
+  rep.ms[2] = ms_since(t0);
+}
+}  // namespace
+
+extern "C" {
+
+const char* r0hip_selftest(uint32_t suites_mask, uint32_t po2, r0hip_selftest_report* out, size_t out_size) {
+  return wrap([&] {
+    const std::string who = "r0hip_selftest: ";
+    R0_REQUIRE(suites_mask >= 1 && suites_mask <= 7,
+               who + "suites_mask " + std::to_string(suites_mask) + " names no suite of bits 0..2");
+    R0_REQUIRE(po2 >= 8 && po2 <= 24, who + "po2 " + std::to_string(po2) + " out of range (8..24)");
+    R0_REQUIRE(out, who + "out is NULL");
+    R0_REQUIRE(out_size == sizeof(r0hip_selftest_report),
+               who + "out_size " + std::to_string(out_size) + " is not sizeof(r0hip_selftest_report) = " +
+                   std::to_string(sizeof(r0hip_selftest_report)));
+    const CircuitDef* c = find_circuit("demo");
+    R0_REQUIRE(c, who + unknown_circuit("demo"));
+    memset(out, 0, sizeof *out);
+    std::string why;
+    for (int suite = 0; suite < 3; suite++)
+      if ((suites_mask >> suite) & 1) selftest_suite(*c, suite, po2, out->suite[suite], why);
+    R0_REQUIRE(why.empty(), who + why);
   });
 }
 

@@ -58,5 +58,15 @@ struct CircuitDef {
 };
 
 const CircuitDef* find_circuit(const std::string& name);
+// every circuit compiled in, in build order (tools/circuit_files.py: the shipped ones, the demo
+// circuit, then those plugged in with EXTRA_CIRCUIT_DIRS)
+size_t circuit_count();
+const CircuitDef& circuit_at(size_t i);
+// "unknown circuit X (compiled in: a, b, c)"
+inline std::string unknown_circuit(const char* name) {
+  std::string m = std::string("unknown circuit ") + (name ? name : "(null)") + " (compiled in: ";
+  for (size_t i = 0; i < circuit_count(); i++) m += (i ? ", " : "") + std::string(circuit_at(i).name);
+  return m + ")";
+}
 
 }  // namespace r0

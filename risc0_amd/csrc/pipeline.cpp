@@ -865,7 +865,7 @@ const char* prove_segments_impl(const char* circuit, int suite, uint32_t po2, in
                                 r0hip_segment_job* jobs, size_t njobs, uint32_t in_flight) {
   try {
     const CircuitDef* c = find_circuit(circuit ? circuit : "");
-    R0_REQUIRE(c, std::string("unknown circuit ") + (circuit ? circuit : "(null)"));
+    R0_REQUIRE(c, unknown_circuit(circuit));
     R0_REQUIRE(suite >= 0 && suite <= 2, "unknown hash suite");
     R0_REQUIRE(po2 >= 1 && po2 <= 24, "po2 out of range");
     R0_REQUIRE(njobs == 0 || jobs, "jobs is NULL");

@@ -21,6 +21,7 @@
 #include "../../include/r0hip.h"
 #include "circuit.h"
 #include "devmem.h"
+#include "plugin.h"
 #include "runtime.h"
 #include "transcript.h"
 
@@ -782,12 +783,14 @@ std::string last_profile() { return g_last_profile; }
 // circuit/rv32im/src/prove/hal/mod.rs:181-224 (recursion: prove/mod.rs:176-226, no version word)
 // `uploads` (optional): the groups may still be uploading; each is waited for just before
 // its first use, so a segment's early phases overlap the upload of its later groups
-std::vector<uint32_t> prove_segment(const CircuitDef& c, int suite, uint32_t po2, const uint32_t* code,
-                                    const uint32_t* data, const uint32_t* accum, uint32_t* global,
-                                    bool write_version, uint32_t version, std::vector<uint32_t>* mix_out,
-                                    const UploadGate* uploads, const AccumStep* acc, GroupWork* code_early,
-                                    const CachedGroup* code_cached) {
+// `cb` (prove_segment_cb): the accum group comes from the caller's function, after the mix
+static std::vector<uint32_t> prove_segment_impl(const CircuitDef& c, int suite, uint32_t po2, const uint32_t* code,
+                                                const uint32_t* data, const uint32_t* accum, uint32_t* global,
+                                                bool write_version, uint32_t version, std::vector<uint32_t>* mix_out,
+                                                const UploadGate* uploads, const AccumStep* acc, GroupWork* code_early,
+                                                const CachedGroup* code_cached, const AccumCallback* cb) {
   R0_REQUIRE(suite >= 0 && suite <= 2, "unknown hash suite");
+  R0_REQUIRE(!cb || (cb->fn && !accum && !acc), "prove_segment: an accum callback beside an accum group or step");
   R0_REQUIRE(!code_cached || (!code_early && !uploads), "prove_segment: a cached code group with one in flight");
   R0_REQUIRE(!acc || (acc->accum && !accum), "prove_segment: give the accum group or an accumulation, not both");
   R0_REQUIRE(po2 >= 2 && po2 <= 24, "po2 out of range");
@@ -864,6 +867,7 @@ std::vector<uint32_t> prove_segment(const CircuitDef& c, int suite, uint32_t po2
   // interpolated out of place, the accumulation only read the data): the constraint polynomial on
   // their rows, with a poly_mix of the OS's, so the transcript and the seal are those of the mode
   // off. A violated row ends the proof here, before the accum commit and the 4N work.
+  DevBuf cb_accum;  // the callback's accum group: alive until the final drain
   auto check_witness = [&](const uint32_t* accum_group) {
     if (!witness_check_mode()) return;
     gate(0);
@@ -899,6 +903,26 @@ std::vector<uint32_t> prove_segment(const CircuitDef& c, int suite, uint32_t po2
     prof.mark("accumulate");
     check_witness(acc->accum);
     p.commit_group(0, acc->accum);  // nothing to wait for: the group never uploads
+  } else if (cb) {
+    // r0hip_prove_segment_cb: the group is the prover's, filled by the caller's function once
+    // the mix is known. The stream is drained first, so the function sees code and data
+    // committed and may write the group by any means; what it queues on `s` is ordered before
+    // the zeroize. A message ends the proof here, as a failed witness check does.
+    Span acc_span("accumulate");
+    const size_t rows = p.cycles, cols = c.group_size(0);
+    cb_accum = DevBuf(rows * cols);
+    HIP_OK(hipMemsetD32Async(cb_accum.p, 0xFFFFFFFFu, rows * cols, s));
+    HIP_OK(hipStreamSynchronize(s));
+    const char* msg = cb->fn(cb->user, mix.data(), cb_accum.p, s);
+    if (msg) {
+      const std::string m = msg;
+      (void)prof.finish();
+      throw std::runtime_error("accum callback: " + m);
+    }
+    eltwise_zeroize(s, cb_accum.p, rows * cols);
+    prof.mark("accumulate");
+    check_witness(cb_accum.p);
+    p.commit_group(0, cb_accum.p);
   } else {
     if (witness_check_mode()) {
       gate(2);
@@ -911,6 +935,22 @@ std::vector<uint32_t> prove_segment(const CircuitDef& c, int suite, uint32_t po2
   HIP_OK(hipStreamSynchronize(s));
   g_last_profile = prof.finish();
   return std::move(p.iop.proof);
+}
+
+std::vector<uint32_t> prove_segment(const CircuitDef& c, int suite, uint32_t po2, const uint32_t* code,
+                                    const uint32_t* data, const uint32_t* accum, uint32_t* global,
+                                    bool write_version, uint32_t version, std::vector<uint32_t>* mix_out,
+                                    const UploadGate* uploads, const AccumStep* acc, GroupWork* code_early,
+                                    const CachedGroup* code_cached) {
+  return prove_segment_impl(c, suite, po2, code, data, accum, global, write_version, version, mix_out, uploads, acc,
+                            code_early, code_cached, nullptr);
+}
+
+std::vector<uint32_t> prove_segment_cb(const CircuitDef& c, int suite, uint32_t po2, const uint32_t* code,
+                                       const uint32_t* data, uint32_t* global, bool write_version, uint32_t version,
+                                       std::vector<uint32_t>* mix_out, const AccumCallback& cb) {
+  return prove_segment_impl(c, suite, po2, code, data, nullptr, global, write_version, version, mix_out, nullptr,
+                            nullptr, nullptr, nullptr, &cb);
 }
 
 }  // namespace r0

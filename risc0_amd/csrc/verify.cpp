@@ -204,7 +204,7 @@ static const char* verify_entry(const char* circuit, int suite, const uint32_t* 
                                 uint32_t* code_root_out, uint32_t* po2_out, vfy::OpeningBackend backend = nullptr) {
   try {
     const CircuitDef* c = find_circuit(circuit ? circuit : "");
-    R0_REQUIRE(c, std::string("unknown circuit ") + (circuit ? circuit : "(null)"));
+    R0_REQUIRE(c, unknown_circuit(circuit));
     R0_REQUIRE(suite >= 0 && suite <= 2, "unknown hash suite");
     R0_REQUIRE(seal || seal_len == 0, "seal is NULL");
     R0_REQUIRE(code_roots || n_code_roots == 0, "code_roots is NULL");
@@ -275,7 +275,7 @@ extern "C" const char* r0hip_constraint_term(const char* circuit, const uint32_t
                                              const uint32_t* h_global, const uint32_t* h_poly_mix, int32_t* term) {
   try {
     const CircuitDef* c = find_circuit(circuit ? circuit : "");
-    R0_REQUIRE(c, std::string("r0hip_constraint_term: unknown circuit ") + (circuit ? circuit : "(null)"));
+    R0_REQUIRE(c, "r0hip_constraint_term: " + unknown_circuit(circuit));
     R0_REQUIRE(h_taps, "r0hip_constraint_term: h_taps is NULL");
     R0_REQUIRE(h_mix, "r0hip_constraint_term: h_mix is NULL");
     R0_REQUIRE(h_global, "r0hip_constraint_term: h_global is NULL");
@@ -294,7 +294,7 @@ extern "C" const char* r0hip_poly_ext(const char* circuit, const uint32_t* h_mix
                                       const uint32_t* h_eval_u, const uint32_t* h_poly_mix, uint32_t* h_out) {
   try {
     const CircuitDef* c = find_circuit(circuit ? circuit : "");
-    R0_REQUIRE(c, std::string("unknown circuit ") + (circuit ? circuit : "(null)"));
+    R0_REQUIRE(c, unknown_circuit(circuit));
     R0_REQUIRE(h_mix && h_global && h_eval_u && h_poly_mix && h_out, "poly_ext: null argument");
     std::vector<FpExt> eval_u(c->n_taps);
     for (size_t i = 0; i < c->n_taps; i++) eval_u[i] = vfy::load_ext(h_eval_u + 4 * i);

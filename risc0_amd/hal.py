@@ -142,6 +142,12 @@ def _declare(L):
         "r0hip_worker_set_preflight_threads": [vp, C.c_uint32, C.POINTER(C.c_uint32)],
         "r0hip_worker_get_stats": [vp, vp, sz],
         "r0hip_rv32im_bigint_accum_inject": [vp, sz, u32p, vp, sz],
+        "r0hip_circuit_info": [C.c_char_p, vp, sz, C.c_char_p, sz],
+        "r0hip_prove_segment_cb": [C.c_char_p, C.c_int, C.c_uint32, vp, vp, vp, vp, vp, C.c_int, C.c_uint32, u32p, sz,
+                                   C.POINTER(sz), u32p],
+        "r0hip_demo_witness": [C.c_uint32, sz, C.c_uint32, C.c_uint32, vp, vp, vp],
+        "r0hip_demo_accum": [C.c_uint32, sz, vp, u32p, vp],
+        "r0hip_selftest": [C.c_uint32, C.c_uint32, vp, sz],
         "r0hip_last_profile": [C.c_char_p, sz],
         "r0hip_set_kernel_timing": [C.c_int],
         "r0hip_kernel_times": [C.c_char_p, sz],
@@ -463,9 +469,7 @@ class HipHal:
 
 def prove_segment(hal, circuit, po2, code, data, accum, glob, version=None, seal_cap=1 << 24):
     """Prove one segment from device-resident witness groups; returns (seal, mix)."""
-    from json import load
-    with open(os.path.join(_HERE, "circuits", circuit + ".taps.json")) as f:
-        mix_size = load(f)["mix_size"]
+    mix_size = circuit_info(circuit)["mix_size"]  # any circuit compiled in, plugged-in ones included
     seal = np.zeros(seal_cap, dtype=np.uint32)
     n = C.c_size_t(0)
     mix = np.zeros(mix_size, dtype=np.uint32)
@@ -473,6 +477,104 @@ def prove_segment(hal, circuit, po2, code, data, accum, glob, version=None, seal
                                     int(version is not None), version or 0, seal.ctypes.data_as(u32p), seal_cap,
                                     C.byref(n), mix.ctypes.data_as(u32p)))
     return seal[: n.value].copy(), mix
+
+
+class CircuitDesc(C.Structure):
+    """struct r0hip_circuit_desc"""
+    _fields_ = [("group_sizes", C.c_uint32 * 3), ("mix_size", C.c_uint32), ("output_size", C.c_uint32),
+                ("n_taps", C.c_uint32), ("info", C.c_uint8 * 16)]
+
+
+def circuit_names():
+    """r0hip_circuit_info(NULL): the circuits compiled into the library, in build order (the shipped
+    ones, "demo", then those plugged in at build time with EXTRA_CIRCUIT_DIRS). Host-only."""
+    buf = C.create_string_buffer(4096)
+    check(lib().r0hip_circuit_info(None, None, 0, buf, 4096))
+    return buf.value.decode().split()
+
+
+def circuit_info(circuit):
+    """r0hip_circuit_info: {"name", "group_sizes" (accum, code, data), "mix_size", "output_size",
+    "n_taps", "info" (16 bytes)} of a circuit compiled in. Host-only."""
+    d = CircuitDesc()
+    check(lib().r0hip_circuit_info(circuit.encode() if circuit is not None else b"", C.byref(d), C.sizeof(d), None, 0))
+    return {"name": circuit, "group_sizes": [int(x) for x in d.group_sizes], "mix_size": int(d.mix_size),
+            "output_size": int(d.output_size), "n_taps": int(d.n_taps), "info": bytes(d.info)}
+
+
+ACCUM_FN = C.CFUNCTYPE(C.c_void_p, C.c_void_p, u32p, C.c_void_p, C.c_void_p)  # r0hip_accum_fn
+
+
+def prove_segment_cb(hal, circuit, po2, code, data, accum_fn, glob, version=None, seal_cap=1 << 24):
+    """r0hip_prove_segment_cb: prove_segment with the accum group made after the mix is drawn.
+    accum_fn(mix, accum, stream) is called on this thread with the mix (numpy, mix_size words), the
+    library's accum group as a Buffer (2^po2 x group_sizes[0] words, INVALID-filled; valid only
+    during the call) and the stream; it fills the group (copy_from, demo_accum, any per-op call) and
+    returns None, or a str that fails the proof. Returns (seal, mix)."""
+    info = circuit_info(circuit)
+    rows, cols, mix_size = 1 << po2, info["group_sizes"][0], info["mix_size"]
+    keep = []  # the message's bytes must outlive the callback's return
+
+    def tramp(_user, h_mix, d_accum, stream):
+        try:
+            mix = np.ctypeslib.as_array(h_mix, shape=(mix_size,)).copy() if mix_size else np.zeros(0, np.uint32)
+            msg = accum_fn(mix, Buffer(hal, "accum", rows * cols, 1, ptr=d_accum, owner=False), stream)
+        except Exception as e:  # never unwind through the C frames
+            msg = f"{type(e).__name__}: {e}"
+        if msg is None:
+            return None
+        keep.append(C.create_string_buffer(str(msg).encode()))
+        return C.addressof(keep[-1])
+
+    fn = ACCUM_FN(tramp)
+    seal = np.zeros(seal_cap, dtype=np.uint32)
+    n = C.c_size_t(0)
+    mix = np.zeros(mix_size, dtype=np.uint32)
+    check(lib().r0hip_prove_segment_cb(circuit.encode(), hal.suite, po2, code.ptr, data.ptr, C.cast(fn, C.c_void_p), None,
+                                       glob.ptr, int(version is not None), version or 0, seal.ctypes.data_as(u32p),
+                                       seal_cap, C.byref(n), mix.ctypes.data_as(u32p)))
+    return seal[: n.value].copy(), mix
+
+
+def demo_witness(po2, n_active, a0, b0, code, data, glob):
+    """r0hip_demo_witness: the demo circuit's code group (every row), the rows below n_active of its
+    data group and its 3 global words, into device Buffers; a0, b0 are Montgomery words."""
+    check(lib().r0hip_demo_witness(po2, n_active, a0, b0, code.ptr, data.ptr, glob.ptr))
+
+
+def demo_accum(po2, n_active, data, mix, accum):
+    """r0hip_demo_accum: the rows below n_active of the demo circuit's accum group from its data
+    group and the 4 mix words (host)."""
+    m, mp = _h(mix)
+    assert m.size == 4
+    check(lib().r0hip_demo_accum(po2, n_active, data.ptr, mp, accum.ptr))
+
+
+class SelftestSuite(C.Structure):
+    """struct r0hip_selftest_suite"""
+    _fields_ = [("passed", C.c_uint32), ("seal_len", C.c_uint32), ("ms", C.c_double * 3)]
+
+
+class SelftestReport(C.Structure):
+    """struct r0hip_selftest_report"""
+    _fields_ = [("suite", SelftestSuite * 3)]
+
+
+def selftest(suites_mask=0b111, po2=10, out_size=None):
+    """r0hip_selftest: prove and verify the demo circuit on this card, per hash suite of the mask
+    (bit 0 poseidon2, 1 sha-256, 2 poseidon254). Returns (error or None, {suite id: {"passed":
+    bits a|b<<1|c<<2, "seal_len", "ms": [a, b, c]}}); error is None only when every check asked
+    for passed. Refusals of the arguments raise R0HipError."""
+    rep = SelftestReport()
+    err = lib().r0hip_selftest(suites_mask, po2, C.byref(rep), C.sizeof(rep) if out_size is None else out_size)
+    msg = None
+    if err:
+        msg = C.cast(err, C.c_char_p).value.decode()
+        lib().r0hip_free_error(err)
+        if not any(s.passed or s.seal_len for s in rep.suite):
+            raise R0HipError(msg)
+    return msg, {i: {"passed": int(s.passed), "seal_len": int(s.seal_len), "ms": [float(x) for x in s.ms]}
+                 for i, s in enumerate(rep.suite) if (suites_mask >> i) & 1}
 
 
 class BigIntBack(C.Structure):

@@ -39,13 +39,22 @@ tuning file; the eval_check family's text does not depend on it.
 import os
 import sys
 
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import circuit_files
+
 ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
 P = 15 * 2**27 + 1
 
 
+def tune_path(circuit):
+    """<circuit>.ectune.json beside the circuit's program (tools/circuit_files.py), or None when
+    the circuit has none: the untuned defaults apply."""
+    return circuit_files.find(circuit, "ectune.json", must=False)
+
+
 def load(circuit):
     prog = []
-    with open(os.path.join(ROOT, "risc0_amd", "circuits", circuit + ".poly.ir")) as f:
+    with open(circuit_files.find(circuit, "poly.ir")) as f:
         for line in f:
             if line.startswith("#") or not line.strip():
                 continue
@@ -359,10 +368,10 @@ def kernel_config(circuit, budget):
     """Per-kernel (waves, prefetch) chosen by tools/tune_eval_check.py on an MI355X and
     committed as risc0_amd/circuits/<circuit>.ectune.json; EC_WAVES/EC_PF (if set) or
     the defaults apply to kernels it does not list (or when EC_NOTUNE is set)."""
-    path = os.path.join(ROOT, "risc0_amd", "circuits", circuit + ".ectune.json")
+    path = tune_path(circuit)
     keep = os.environ.get("EC_KEEPTUNE") == "1"  # EC_WAVES/EC_PF override only those two fields
     if (os.environ.get("EC_NOTUNE") or (not keep and ("EC_WAVES" in os.environ or "EC_PF" in os.environ))
-            or not os.path.exists(path)):
+            or path is None):
         return {}
     import json
     with open(path) as f:
@@ -420,8 +429,8 @@ def mat_config(circuit, budget):
     <circuit>.ectune.json as "mat"), so kernels read them instead of recomputing their cones.
     Applies whatever EC_WAVES/EC_PF say, since tuning variants must share the partition;
     EC_NOMAT=1 disables it."""
-    path = os.path.join(ROOT, "risc0_amd", "circuits", circuit + ".ectune.json")
-    if os.environ.get("EC_NOMAT") == "1" or not os.path.exists(path):
+    path = tune_path(circuit)
+    if os.environ.get("EC_NOMAT") == "1" or path is None:
         return []
     import json
     with open(path) as f:
@@ -440,8 +449,8 @@ def resplit_config(circuit, budget):
     spec = os.environ.get("EC_RESPLIT")
     over = {}
     if spec is None:
-        path = os.path.join(ROOT, "risc0_amd", "circuits", circuit + ".ectune.json")
-        if not os.path.exists(path):
+        path = tune_path(circuit)
+        if path is None:
             return {}, {}
         import json
         with open(path) as f:
