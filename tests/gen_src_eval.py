@@ -60,10 +60,12 @@ def _inv(x):
     return np.array([pow(int(a), P - 2, P) * R % P * R % P if a else 0 for a in x], np.int64)
 
 
-def run_kernel(src, bufs, rows, steps, vals=None):
+def run_kernel(src, bufs, rows, steps, vals=None, on_batch=None):
     """Execute one generated kernel's statements for cycles [0, steps); bufs are the AccArgs
     arrays (numpy uint32, updated in place by the stores); vals (recursion) the per-cycle
-    FpExt of A.vals, int64 Montgomery words of shape (steps, 4)."""
+    FpExt of A.vals, int64 Montgomery words of shape (steps, 4). on_batch(xs, live), if given,
+    is called at each fp_inv_batch with its inputs (one array per element) and the mask of the
+    cycles that reach it."""
     cyc = np.arange(steps, dtype=np.int64)
     v, ib, rr, t = {}, {}, {}, {}
 
@@ -106,6 +108,8 @@ def run_kernel(src, bufs, rows, steps, vals=None):
             assert len(names) == int(g[1])
             ib[int(g[0])] = [v[n] for n in names]
         elif kind == "ibrun":
+            if on_batch is not None:
+                on_batch(ib[int(g[0])], mask[-1])
             ib[int(g[0])] = [_inv(x) for x in ib[int(g[0])]]  # Montgomery's trick is exact
         elif kind == "ibget":
             v[int(g[0])] = ib[int(g[1])][int(g[2])]

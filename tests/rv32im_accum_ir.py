@@ -22,8 +22,10 @@ def load():
     return ops
 
 
-def run(data, accum, glob, mix, rows, last_cycle, ops=None):
-    """accum (column-major words) updated in place for cycles [0, last_cycle)"""
+def run(data, accum, glob, mix, rows, last_cycle, ops=None, on_inv=None):
+    """accum (column-major words) updated in place for cycles [0, last_cycle); on_inv(x, live),
+    if given, is called at each `i` op with its input words and the mask of the cycles whose
+    enclosing `if` blocks are all taken"""
     ops = ops or load()
     bufs = [data, accum, glob, mix]
     cyc = np.arange(last_cycle, dtype=np.int64)
@@ -48,6 +50,8 @@ def run(data, accum, glob, mix, rows, last_cycle, ops=None):
             v[op[1]] = (-v[op[2]]) % P
         elif o == "i":
             x = v[op[2]]
+            if on_inv is not None:
+                on_inv(x, mask[-1])
             v[op[1]] = np.array([pow(int(a), P - 2, P) * R % P * R % P if a else 0 for a in x], np.int64)
         elif o == "z":
             v[op[1]] = np.where(v[op[2]] == 0, R, 0).astype(np.int64)

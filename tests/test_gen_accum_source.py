@@ -55,6 +55,43 @@ def test_generated_source_matches_ir(tmp_path, limit, inv_batch, ahead, extra, r
         assert any("fp_inv_batch" in k for k in kernels)
 
 
+@pytest.fixture(scope="module")
+def build_kernels(tmp_path_factory):
+    """the rv32im step kernels of the build's settings (risc0_amd/csrc/Makefile's defaults)"""
+    return _generate(str(tmp_path_factory.mktemp("rv_build")), 1200, 8, 64)
+
+
+@pytest.mark.parametrize("kind,mix_kind", [("max", "same"), ("max", "holes"), ("mixed", "same"), ("mixed", "holes")])
+def test_generated_source_worst_case_words(build_kernels, kind, mix_kind):
+    """The inputs of test_accum_edges_gpu.test_rv32im_step_worst_case_words (tests/accum_edges.py)
+    at 64 rows, arms r % 13, through the emitted source of the build's settings: `max` drives
+    every fused 64-bit sum to the bound fuse_sums folds by (the interpreter asserts that none
+    wraps and that REDC's input stays below p * 2^32); `holes` hands one fp_inv_batch zero and
+    non-zero inputs on the same cycle. A failure of the GPU test that passes here is the device
+    code's, not the generator's."""
+    import accum_edges as E
+    rows = 64
+    data, glob, mix = E.rv_case(5, rows, np.arange(rows) % 13, kind, mix_kind)
+    want = E.rv_step_reference(data, glob, mix, rows, rows)
+    got = np.full(103 * rows, 0xFFFFFFFF, np.uint32)
+    bufs = [data.copy(), got, glob, mix]
+    batches = {"n": 0, "both": 0}
+
+    def on_batch(xs, live):
+        zero = np.stack([x == 0 for x in xs])
+        batches["n"] += 1
+        batches["both"] += bool((live & zero.any(0) & ~zero.all(0)).any())
+
+    for src in build_kernels:
+        GS.run_kernel(src, bufs, rows, rows, on_batch=on_batch)
+    bad = np.nonzero(got != want)[0]
+    assert bad.size == 0, f"{bad.size} words differ; first at col {bad[0] // rows} row {bad[0] % rows}"
+    assert batches["n"] > 0
+    if mix_kind == "holes":
+        assert batches["both"] > 0, "no batch of inverses saw a zero beside a non-zero input"
+    print(f"{kind}/{mix_kind}: {batches['both']} of {batches['n']} inverse batches mix zero and non-zero inputs")
+
+
 def _generate_recursion(tmp, ahead):
     out = os.path.join(tmp, f"rec_{ahead}")
     subprocess.check_call([sys.executable, os.path.join(ROOT, "tools", "gen_accum.py"), "recursion", out,
