@@ -1026,8 +1026,11 @@ const char* r0hip_constraint_term(const char* circuit, const uint32_t* h_taps, c
  * r0hip_constraint_term, r0hip_prove_segment, r0hip_prove_segment_cb, r0hip_prove_segments,
  * r0hip_verify_seal*, the testing variants) take any name the library was built with: "rv32im",
  * "recursion", "demo", and every circuit of the directories given to the build as
- * EXTRA_CIRCUIT_DIRS ("Adding a circuit / checking a card"). An unknown name's
- * error lists the names compiled in. The rv32im version word and the two device accumulations
+ * EXTRA_CIRCUIT_DIRS ("Adding a circuit / checking a card"), and every circuit
+ * registered at run time (r0hip_circuit_register, below). An unknown name's error lists the names
+ * compiled in and, once there are any, the registered ones after them
+ * ("(compiled in: rv32im, recursion, demo; registered: x)"); r0hip_circuit_info with a NULL circuit
+ * lists both sets, compiled in first. The rv32im version word and the two device accumulations
  * (r0hip_prove_segment_accum) stay tied to their circuits' names.
  * r0hip_circuit_info: what a caller needs to size a circuit's buffers. circuit = NULL: the names,
  * space-separated in build order, into names (names_cap bytes, NUL-terminated; too small is an
@@ -1043,6 +1046,63 @@ typedef struct r0hip_circuit_desc {
 /* [host-only] */
 const char* r0hip_circuit_info(const char* circuit, r0hip_circuit_desc* out, size_t out_size, char* names,
                                size_t names_cap);
+
+/* ---- circuits registered at run time ----
+ * r0hip_circuit_register: a circuit's tables handed over while the process runs, for a circuit
+ * the library was not built with ("A circuit at run time"). From then on every
+ * circuit-generic entry point above takes the name, as it takes a compiled-in one; eval_check and
+ * the constraint-rows check run an interpreter of the constraint program on the device, which is
+ * several times slower than the kernels a build generates. The fields mirror the tables of a
+ * compiled-in circuit (tools/gen_circuits_inc.py writes the same arrays from <name>.taps.json and
+ * <name>.poly.ir):
+ *   taps        n_taps x {offset, back, group, combo, skip}, sorted by group, offset, back
+ *   eval_args   per eval_check argument: 0 accum, 1 code, 2 data, -1 mix, -2 global
+ *   ir          n_ir records {op, dst, a, b, c, d}, op the index into "celg+-*abr", dst dense
+ *               from 0 (the `r` record, last, names the result in dst): c {word}, e {4 words}
+ *               (Montgomery, below p), l {tap index}, g {0 mix | 1 global, word index},
+ *               + - * {id, id}, a {acc, x, power}, b {acc, x, y, power}
+ * t_size = sizeof(r0hip_circuit_tables). Everything is copied; the copy lives until the process
+ * ends and there is no way to take a circuit out (proofs in flight hold it). Safe from several
+ * threads; needs no GPU and no r0hip_init. Refused, with the field named and the registry
+ * unchanged: a name that is not a C identifier of at most 31 characters or is taken; more than 64
+ * registrations; taps out of order or whose skips do not tile the registers; combo_begin,
+ * group_begin (n_groups = 3) or group_sizes that disagree with the taps; eval_args outside the
+ * five values or more than 16 of them; mix_size or output_size of 2^24 or more; n_ir = 0 or above
+ * 2^20; and in ir: an op outside the ten, a dst that is not dense, an operand id that is not below
+ * its record's dst, no `r` record or one that is not last, an l whose tap index is not below
+ * n_taps or whose group eval_args lacks, a g whose word index is not below mix_size or
+ * output_size, an a or b whose power is not below n_poly_mix or whose acc is not an FpExt value
+ * (c, l, g are Fp; e, a, b FpExt; + - * the wider operand's), a constant word of p or more.
+ * The rv32im version word, the two device accumulations (r0hip_prove_segment_accum refuses a
+ * registered circuit) and the witness generators stay tied to the compiled-in names. */
+typedef struct r0hip_circuit_tables {
+  const char* name;
+  const uint32_t* taps;
+  size_t n_taps;
+  const uint32_t* combo_taps;
+  size_t n_combo_taps;
+  const uint32_t* combo_begin; /* combos_count + 1 */
+  size_t combos_count;
+  const uint32_t* group_begin; /* n_groups + 1 */
+  size_t n_groups;
+  const uint32_t* group_sizes; /* n_groups */
+  const uint32_t* poly_mix_powers;
+  size_t n_poly_mix;
+  uint8_t info[16]; /* the circuit's CircuitInfo bytes */
+  size_t mix_size;
+  size_t output_size;
+  const int32_t* eval_args;
+  size_t n_eval_args;
+  const uint32_t* ir; /* 6 * n_ir words */
+  size_t n_ir;
+} r0hip_circuit_tables;
+/* [host-only] */
+const char* r0hip_circuit_register(const r0hip_circuit_tables* t, size_t t_size);
+/* TESTING ONLY: the points one launch of the interpreter takes on the calling thread, in place of
+ * the chunk its slot-file budget gives; 0 = the budget's own choice, which
+ * every new thread starts with. *was (may be NULL) = the previous value. */
+/* [host-only] */
+const char* r0hip_testing_set_interp_chunk(uint32_t points, uint32_t* was);
 
 /* r0hip_prove_segment with the accum group made after the mix is drawn, for a circuit whose
  * accumulation the library does not have. The library commits code and data, draws the

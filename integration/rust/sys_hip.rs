@@ -47,6 +47,31 @@ pub struct R0HipCircuitDesc {
     pub info: [u8; 16],
 }
 
+/// struct r0hip_circuit_tables: a circuit handed to r0hip_circuit_register at run time (the
+/// library copies every array).
+#[repr(C)]
+pub struct R0HipCircuitTables {
+    pub name: *const c_char,
+    pub taps: *const u32,
+    pub n_taps: usize,
+    pub combo_taps: *const u32,
+    pub n_combo_taps: usize,
+    pub combo_begin: *const u32,
+    pub combos_count: usize,
+    pub group_begin: *const u32,
+    pub n_groups: usize,
+    pub group_sizes: *const u32,
+    pub poly_mix_powers: *const u32,
+    pub n_poly_mix: usize,
+    pub info: [u8; 16],
+    pub mix_size: usize,
+    pub output_size: usize,
+    pub eval_args: *const i32,
+    pub n_eval_args: usize,
+    pub ir: *const u32,
+    pub n_ir: usize,
+}
+
 /// r0hip_accum_fn: fills the accum group once the mix is known; NULL, or a message that fails the proof.
 pub type R0HipAccumFn = Option<
     unsafe extern "C" fn(user: *mut c_void, h_mix: *const u32, d_accum: *mut u32, stream: *mut c_void) -> *const c_char,
@@ -817,6 +842,10 @@ unsafe extern "C" {
         names: *mut c_char,
         names_cap: usize,
     ) -> *const c_char;
+    // host-only: a circuit registered at run time (interpreted eval_check), and the testing-only
+    // points per interpreter launch
+    pub fn r0hip_circuit_register(t: *const R0HipCircuitTables, t_size: usize) -> *const c_char;
+    pub fn r0hip_testing_set_interp_chunk(points: u32, was: *mut u32) -> *const c_char;
     pub fn r0hip_prove_segment_cb(
         circuit: *const c_char,
         suite: c_int,

@@ -17,7 +17,8 @@ from .hal import (POSEIDON2, POSEIDON254, SHA256, BigIntBack, Buffer, HipHal, R0
                   recursion_last_preflight_ms, Opening, merkle_open_digests, set_verify_device_poseidon254,
                   VERIFY_RECEIPTS_DEVICE, ConstraintReport,
                   constraint_rows, constraint_term, set_witness_check, circuit_names, circuit_info,
-                  prove_segment_cb, demo_witness, demo_accum, selftest, CircuitDesc, SelftestReport)
+                  prove_segment_cb, demo_witness, demo_accum, selftest, CircuitDesc, SelftestReport,
+                  CircuitTables, circuit_tables_struct, register_circuit, testing_set_interp_chunk)
 
 __all__ = ["POSEIDON2", "POSEIDON254", "SHA256", "BigIntBack", "bigint_accum_inject", "bigint_accum_states", "bigint_accum_states_device", "bigint_backs", "BIGINT_BACK_DTYPE", "prove_recursion", "recursion_witgen", "rv32im_witgen", "prove_segment_trace", "ResidentTrace", "prove_segment_trace_resident", "Buffer", "HipHal", "R0HipError", "check", "exported_symbols", "last_profile",
            "lib", "mem_reset_peak", "mem_stats", "trim", "prove_segment", "prove_segment_accum", "prove_segments",
@@ -29,4 +30,5 @@ __all__ = ["POSEIDON2", "POSEIDON254", "SHA256", "BigIntBack", "bigint_accum_inj
            "recursion_last_preflight_ms", "Opening", "merkle_open_digests", "set_verify_device_poseidon254",
            "VERIFY_RECEIPTS_DEVICE",
            "ConstraintReport", "constraint_rows", "constraint_term", "set_witness_check", "circuit_names", "circuit_info",
-           "prove_segment_cb", "demo_witness", "demo_accum", "selftest", "CircuitDesc", "SelftestReport"]
+           "prove_segment_cb", "demo_witness", "demo_accum", "selftest", "CircuitDesc", "SelftestReport",
+           "CircuitTables", "circuit_tables_struct", "register_circuit", "testing_set_interp_chunk"]

@@ -25,6 +25,7 @@
 #include "backs.h"
 #include "circuit.h"
 #include "devmem.h"
+#include "eval_interp.h"
 #include "plugin.h"
 #include "recursion_preflight.h"
 #include "runtime.h"
@@ -178,6 +179,12 @@ const char* r0hip_set_witness_check(int on, int* was) {
   return wrap_nosync([&] {
     const bool w = set_witness_check_mode(on != 0);
     if (was) *was = w ? 1 : 0;
+  });
+}
+const char* r0hip_testing_set_interp_chunk(uint32_t points, uint32_t* was) {
+  return wrap_nosync([&] {
+    const uint32_t w = set_interp_test_chunk(points);
+    if (was) *was = w;
   });
 }
 const char* r0hip_call_stats(uint64_t* out) {

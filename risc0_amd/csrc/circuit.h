@@ -12,6 +12,10 @@
 
 namespace r0 {
 
+namespace rt {
+struct Programs;  // circuit_rt.h
+}
+
 struct CircuitDef {
   const char* name;
   const uint32_t* taps;  // n_taps x {offset, back, group, combo, skip}
@@ -38,6 +42,10 @@ struct CircuitDef {
   // {op, dst, a, b, c, d}, op index into "celg+-*abr", dst dense 0..n_ir-1
   const uint32_t* ir;
   size_t n_ir;
+  // A circuit registered at run time (r0hip_circuit_register, circuit_registry.cpp): the four
+  // kernel pointers above are null and the device interprets these programs (eval_interp.hip).
+  // Null for every compiled-in circuit.
+  const rt::Programs* interp = nullptr;
 
   struct Tap {
     uint32_t offset, back, group, combo, skip;
@@ -57,16 +65,24 @@ struct CircuitDef {
   }
 };
 
+// The circuits compiled in, in build order (tools/circuit_files.py: the shipped ones, the demo
+// circuit, then those plugged in with EXTRA_CIRCUIT_DIRS). gen/circuits.cpp defines these three;
+// the generator writes them as find_circuit, circuit_count and circuit_at, as it did before there
+// was a registry, and Makefile.objs renames them for that one file.
+const CircuitDef* compiled_find_circuit(const std::string& name);
+size_t compiled_circuit_count();
+const CircuitDef& compiled_circuit_at(size_t i);
+
+// Every circuit the process knows (circuit_registry.cpp): the compiled-in ones, then those
+// registered at run time in registration order. Readers take no lock: the registry is an
+// append-only table of kMaxRegistered entries behind an atomic count, and an entry never moves
+// or goes away.
+constexpr size_t kMaxRegistered = 64;
 const CircuitDef* find_circuit(const std::string& name);
-// every circuit compiled in, in build order (tools/circuit_files.py: the shipped ones, the demo
-// circuit, then those plugged in with EXTRA_CIRCUIT_DIRS)
 size_t circuit_count();
 const CircuitDef& circuit_at(size_t i);
-// "unknown circuit X (compiled in: a, b, c)"
-inline std::string unknown_circuit(const char* name) {
-  std::string m = std::string("unknown circuit ") + (name ? name : "(null)") + " (compiled in: ";
-  for (size_t i = 0; i < circuit_count(); i++) m += (i ? ", " : "") + std::string(circuit_at(i).name);
-  return m + ")";
-}
+// "unknown circuit X (compiled in: a, b, c)", and once anything is registered
+// "unknown circuit X (compiled in: a, b, c; registered: d)"
+std::string unknown_circuit(const char* name);
 
 }  // namespace r0

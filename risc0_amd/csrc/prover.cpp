@@ -21,6 +21,7 @@
 #include "../../include/r0hip.h"
 #include "circuit.h"
 #include "devmem.h"
+#include "eval_interp.h"
 #include "plugin.h"
 #include "runtime.h"
 #include "transcript.h"
@@ -350,6 +351,35 @@ void ec_tables(const CircuitDef& c, const EvalCheckInfo& info, const uint32_t* c
   e.mat_ext = static_cast<uint32_t*>(scratch(size_t(info.mat_ext) * domain * 16 + 16, kSlotEcMatExt));
   e.domain = uint32_t(domain);
 }
+
+// A circuit registered at run time has no generated kernels: its constraint program is
+// interpreted (eval_interp.hip) over n points, the eval_check form into `check` or the rows form
+// into `acc`. The poly_mix table is map_pow(poly_mix, poly_mix_powers) and nothing else. The
+// records, tap tables and constants are resident for the life of the process, as the circuit is.
+struct InterpRun {
+  const rt::Programs& p;
+  uint32_t lanes;
+};
+InterpRun run_interp(const CircuitDef& c, bool rows, const uint32_t* const* groups, const uint32_t* mix,
+                     const uint32_t* global, FpExt poly_mix, size_t n, const uint32_t* vinv, uint32_t* check,
+                     uint32_t* acc) {
+  const rt::Programs& p = *c.interp;
+  std::vector<const uint32_t*> args(c.n_eval_args);
+  for (size_t i = 0; i < c.n_eval_args; i++) {
+    const int a = c.eval_args[i];
+    args[i] = a >= 0 ? groups[a] : (a == -1 ? mix : global);
+    R0_REQUIRE(args[i] || (a == -1 && !c.mix_size) || (a == -2 && !c.output_size),
+               std::string(rows ? "constraint_rows" : "eval_check") + ": argument " + std::to_string(i) + " of circuit " +
+                   c.name + " is NULL");
+  }
+  const uint32_t* image = dev_table(std::string("interp:") + c.name, [&] { return interp_device_image(p); });
+  const auto* d_args = reinterpret_cast<const uint32_t* const*>(upload(args, kSlotEcColPtr));
+  const uint32_t* d_pow = upload(map_pow(poly_mix, c.poly_mix_powers, c.n_poly_mix), kSlotEcPolyMix);
+  const uint32_t lanes = interp_chunk_points(p, n);
+  auto* slots = static_cast<uint32_t*>(scratch(size_t(lanes) * p.slot_words() * 4 + 16, kSlotEcInterp));
+  eval_interp(stream(), rows, p, image, d_args, d_pow, n, slots, lanes, vinv, check, acc);
+  return InterpRun{p, lanes};
+}
 }  // namespace
 
 // eval_check for one circuit (rv32im/src/prove/hal/cpu.rs:145-207 semantics)
@@ -357,13 +387,7 @@ void run_eval_check(const CircuitDef& c, uint32_t* check, const uint32_t* const*
                     const uint32_t* global, FpExt poly_mix, size_t po2, const uint32_t* h_mix,
                     const uint32_t* h_global) {
   hipStream_t s = stream();
-  EvalCheckInfo info;
-  c.info(&info);
   size_t steps = size_t(1) << po2, domain = steps * INV_RATE;
-  std::vector<uint32_t> hm, hg;
-  std::vector<const uint32_t*> args;
-  EvalCheckArgs e;
-  ec_tables(c, info, groups, mix, global, poly_mix, domain, h_mix, h_global, hm, hg, args, e);
   // inv((3 * w_D^c)^N - 1) depends only on c mod 4 (w_D^(cN) = w_4^c)
   std::vector<uint32_t> vinv(4);
   uint32_t w = fp_encode(kRouFwd[po2 + 2]);
@@ -372,6 +396,20 @@ void run_eval_check(const CircuitDef& c, uint32_t* check, const uint32_t* const*
     uint32_t y = fp_pow(fp_mul(fp_encode(3), x), steps);
     vinv[q] = fp_inv(fp_sub(y, kOne));
   }
+  if (c.interp) {  // registered at run time: the interpreter, same algorithmic bytes
+    double bytes = 16.0 * domain;
+    for (int g = 0; g < 3; g++) bytes += 4.0 * domain * c.group_sizes[g];
+    Span span("eval_check");
+    KScope ks("eval_check_interp", bytes, double(domain) * (c.interp->modmuls + 4));
+    run_interp(c, false, groups, mix, global, poly_mix, domain, upload(vinv, kSlotEcVinv), check, nullptr);
+    return;
+  }
+  EvalCheckInfo info;
+  c.info(&info);
+  std::vector<uint32_t> hm, hg;
+  std::vector<const uint32_t*> args;
+  EvalCheckArgs e;
+  ec_tables(c, info, groups, mix, global, poly_mix, domain, h_mix, h_global, hm, hg, args, e);
   e.vinv = upload(vinv, kSlotEcVinv);
   e.acc = static_cast<uint32_t*>(scratch(domain * 16, kSlotEcAcc));
   e.check = check;
@@ -400,19 +438,26 @@ void constraint_rows_run(const CircuitDef& c, size_t po2, const uint32_t* const*
                          const uint32_t* global, const uint32_t* h_mix, const uint32_t* h_global, FpExt poly_mix,
                          uint32_t* vals, r0hip_constraint_report* report) {
   hipStream_t s = stream();
-  EvalCheckInfo info;
-  c.rows_info(&info);
   const size_t rows = size_t(1) << po2;
   std::vector<uint32_t> hm, hg;
   std::vector<const uint32_t*> args;
   EvalCheckArgs e;
-  ec_tables(c, info, groups, mix, global, poly_mix, rows, h_mix, h_global, hm, hg, args, e);
   e.acc = vals ? vals : static_cast<uint32_t*>(scratch(rows * 16, kSlotEcAcc));
-  e.check = nullptr;
-  e.vinv = nullptr;
-  e.wide = 0;
   auto* d_rep = static_cast<uint32_t*>(scratch(19 * 4, kSlotRowsReport));
-  {
+  if (c.interp) {  // registered at run time: the interpreter, then the same report kernel
+    double bytes = 16.0 * rows;
+    for (int g = 0; g < 3; g++) bytes += 4.0 * rows * c.group_sizes[g];
+    Span span("constraint_rows");
+    KScope ks("constraint_rows_interp", bytes, double(rows) * c.interp->modmuls);
+    run_interp(c, true, groups, mix, global, poly_mix, rows, nullptr, nullptr, e.acc);
+    rows_report(s, e.acc, rows, d_rep);
+  } else {
+    EvalCheckInfo info;
+    c.rows_info(&info);
+    ec_tables(c, info, groups, mix, global, poly_mix, rows, h_mix, h_global, hm, hg, args, e);
+    e.check = nullptr;
+    e.vinv = nullptr;
+    e.wide = 0;
     double bytes = 16.0 * rows;
     for (int g = 0; g < 3; g++) bytes += 4.0 * rows * c.group_sizes[g];
     Span span("constraint_rows");

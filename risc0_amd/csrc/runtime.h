@@ -73,6 +73,7 @@ enum ScratchSlot : int {
   kSlotEcMatExt = 24,
   kSlotEcPolyMixNb = 25,
   kSlotEcColPtr = 26,
+  kSlotEcInterp = 28,   // the interpreter's slot file (eval_interp.hip), a run-time circuit's only
   kSlotEcUniform = 27,  // prover uploads (prover.cpp): evaluation points per group (3 groups), check points,
   // mix_poly_coeffs row lists, combos deltas, query gather tables
   kSlotTapXs = 33,  // .. 35

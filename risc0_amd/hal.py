@@ -143,6 +143,8 @@ def _declare(L):
         "r0hip_worker_get_stats": [vp, vp, sz],
         "r0hip_rv32im_bigint_accum_inject": [vp, sz, u32p, vp, sz],
         "r0hip_circuit_info": [C.c_char_p, vp, sz, C.c_char_p, sz],
+        "r0hip_circuit_register": [vp, sz],
+        "r0hip_testing_set_interp_chunk": [C.c_uint32, u32p],
         "r0hip_prove_segment_cb": [C.c_char_p, C.c_int, C.c_uint32, vp, vp, vp, vp, vp, C.c_int, C.c_uint32, u32p, sz,
                                    C.POINTER(sz), u32p],
         "r0hip_demo_witness": [C.c_uint32, sz, C.c_uint32, C.c_uint32, vp, vp, vp],
@@ -502,6 +504,58 @@ def circuit_info(circuit):
             "output_size": int(d.output_size), "n_taps": int(d.n_taps), "info": bytes(d.info)}
 
 
+class CircuitTables(C.Structure):
+    """struct r0hip_circuit_tables"""
+    _fields_ = [("name", C.c_char_p), ("taps", u32p), ("n_taps", C.c_size_t), ("combo_taps", u32p),
+                ("n_combo_taps", C.c_size_t), ("combo_begin", u32p), ("combos_count", C.c_size_t),
+                ("group_begin", u32p), ("n_groups", C.c_size_t), ("group_sizes", u32p), ("poly_mix_powers", u32p),
+                ("n_poly_mix", C.c_size_t), ("info", C.c_uint8 * 16), ("mix_size", C.c_size_t),
+                ("output_size", C.c_size_t), ("eval_args", C.POINTER(C.c_int32)), ("n_eval_args", C.c_size_t),
+                ("ir", u32p), ("n_ir", C.c_size_t)]
+
+
+def circuit_tables_struct(t, name=None):
+    """The r0hip_circuit_tables of a circuit_tables.load() dict, and the arrays it points into
+    (keep them alive for as long as the struct is used)."""
+    keep = {k: np.ascontiguousarray(t[k], dtype=np.uint32) for k in
+            ("taps", "combo_taps", "combo_begin", "group_begin", "group_sizes", "poly_mix_powers", "ir")}
+    keep["eval_args"] = np.ascontiguousarray(t["eval_args"], dtype=np.int32)
+    s = CircuitTables()
+    s.name = (name if name is not None else t["name"]).encode()
+    for k, a in keep.items():
+        setattr(s, k, a.ctypes.data_as(C.POINTER(C.c_int32) if k == "eval_args" else u32p))
+    s.n_taps, s.n_combo_taps, s.combos_count = t["n_taps"], len(t["combo_taps"]), t["combos_count"]
+    s.n_groups, s.n_poly_mix, s.n_eval_args, s.n_ir = t["n_groups"], len(t["poly_mix_powers"]), len(t["eval_args"]), t["n_ir"]
+    s.mix_size, s.output_size = t["mix_size"], t["output_size"]
+    info = t["circuit_info"].encode() if isinstance(t["circuit_info"], str) else bytes(t["circuit_info"])
+    if len(info) != 16:
+        raise R0HipError(f"circuit_info: {t['circuit_info']!r} is not 16 bytes")
+    s.info = (C.c_uint8 * 16)(*info)
+    return s, keep
+
+
+def register_circuit(name, directory, files=None):
+    """r0hip_circuit_register: make the circuit of <directory>/<name>.poly.ir and <name>.taps.json
+    (the two files a build-time plug-in is; `files` names them when they are not called <name>)
+    known to this process under `name`. Every
+    circuit-generic call then takes the name; its eval_check and constraint-rows check are
+    interpreted on the device, slower than a circuit that was compiled in. The library validates
+    the tables and raises with the field named. Host-only."""
+    from . import circuit_tables
+    base = os.path.join(directory, files if files is not None else name)
+    t = circuit_tables.load(base + ".taps.json", base + ".poly.ir")
+    s, keep = circuit_tables_struct(t, name)
+    check(lib().r0hip_circuit_register(C.byref(s), C.sizeof(s)))
+
+
+def testing_set_interp_chunk(points):
+    """r0hip_testing_set_interp_chunk (TESTING ONLY): the points per interpreter launch on this
+    thread, 0 = the slot-file budget's choice; returns the previous value."""
+    was = C.c_uint32(0)
+    check(lib().r0hip_testing_set_interp_chunk(points, C.byref(was)))
+    return int(was.value)
+
+
 ACCUM_FN = C.CFUNCTYPE(C.c_void_p, C.c_void_p, u32p, C.c_void_p, C.c_void_p)  # r0hip_accum_fn
 
 
@@ -648,9 +702,7 @@ def prove_segment_accum(hal, circuit, po2, code, data, accum, work_cycles, glob,
     trace's BigInt backs [(row, poly_op, coeff, bytes16)], injected with the drawn mix.
     Returns (seal, mix)."""
     backs = bigint_backs(bigint)
-    from json import load
-    with open(os.path.join(_HERE, "circuits", circuit + ".taps.json")) as f:
-        mix_size = load(f)["mix_size"]
+    mix_size = circuit_info(circuit)["mix_size"]  # any circuit the library knows, registered ones included
     seal = np.zeros(seal_cap, dtype=np.uint32)
     n = C.c_size_t(0)
     mix = np.zeros(mix_size, dtype=np.uint32)
@@ -1478,9 +1530,7 @@ def prove_segments(hal, circuit, po2, witnesses, version=None, in_flight=2, seal
     be None: the prover then runs the accumulation on the device (r0hip_prove_segment_accum's
     path) and nothing of that group crosses PCIe; a 5th element then gives the job's BigInt
     backs [(row, poly_op, coeff, bytes16)]."""
-    from json import load
-    with open(os.path.join(_HERE, "circuits", circuit + ".taps.json")) as f:
-        mix_size = load(f)["mix_size"]
+    mix_size = circuit_info(circuit)["mix_size"]  # any circuit the library knows, registered ones included
     jobs = (SegmentJob * len(witnesses))()
     keep, seals, mixes = [], [], []
     for j, w in zip(jobs, witnesses):
