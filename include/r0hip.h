@@ -1098,6 +1098,45 @@ typedef struct r0hip_circuit_tables {
 } r0hip_circuit_tables;
 /* [host-only] */
 const char* r0hip_circuit_register(const r0hip_circuit_tables* t, size_t t_size);
+
+/* ---- circuit modules: a circuit's generated kernels loaded at run time ----
+ * There are three ways to bring a circuit in, and r0hip_circuit_backend tells them apart:
+ *   0  compiled in (the shipped circuits, the demo, EXTRA_CIRCUIT_DIRS): the generated kernels,
+ *      in a library built for them; for a deployment that builds its own libr0hip.so;
+ *   1  registered (r0hip_circuit_register): no build at all, the device interprets the program,
+ *      several times slower; for developing a circuit;
+ *   2  a module (r0hip_circuit_load): the same generated kernels as 0, compiled once into a
+ *      shared object of their own (`make -C risc0_amd/csrc module NAME=x DIR=dir
+ *      OUT=path/x.r0mod.so`, r0hip_module.h) and handed to a stock library while it runs; for
+ *      proving a circuit of one's own at production speed.
+ * r0hip_circuit_load opens path with dlopen(RTLD_NOW | RTLD_LOCAL), reads the descriptor its one
+ * exported function returns, and checks, in this order: the ABI number and the three struct
+ * sizes the module was compiled with (both values are printed), its architecture against the
+ * library's, its tables exactly as r0hip_circuit_register checks them (the same words, the field
+ * named), and what its kernels say of themselves (info() and rows_info(): nargs against
+ * eval_args, every column inside the witness group it names, every folded product's power index
+ * below npm, npm within poly_mix_powers, mat_fp, mat_ext and kernels within the driver's
+ * limits). Only then is the circuit appended to the registry, under the name in its tables,
+ * which name_out (may be NULL; name_cap >= 32 otherwise) receives. From then on every
+ * circuit-generic entry point takes the name and runs the module's kernels, word for word as a
+ * compiled-in circuit's; the interpreter plays no part. A refusal names the path and the reason
+ * ("r0hip_circuit_load: <path>: <reason>"), closes the file again and leaves the registry
+ * unchanged: a file that is missing or no shared object (the loader's message is quoted), no
+ * entry symbol, a name that is taken (a second load of the same file falls here), the 64-entry
+ * limit it shares with r0hip_circuit_register, and the checks above. A loaded module is never
+ * closed. Loading runs the module's code, exactly as linking it would. Safe from several
+ * threads; needs no GPU and no r0hip_init. What refuses a registered circuit refuses a loaded
+ * one with the same words (r0hip_prove_segment_accum, the witness generators, the rv32im version
+ * word stay tied to the compiled-in names).
+ * In the unknown-circuit message and in r0hip_circuit_info's list, loaded names stand among the
+ * registered ones in the order they arrived, and the message's word for both is "registered"
+ * ("(compiled in: rv32im, recursion, demo; registered: x, y)"). */
+/* [host-only] */
+const char* r0hip_circuit_load(const char* path, char* name_out, size_t name_cap);
+/* *kind = 0 compiled in, 1 registered (interpreted), 2 a module; an unknown name is an error. */
+/* [host-only] */
+const char* r0hip_circuit_backend(const char* circuit, int* kind);
+
 /* TESTING ONLY: the points one launch of the interpreter takes on the calling thread, in place of
  * the chunk its slot-file budget gives; 0 = the budget's own choice, which
  * every new thread starts with. *was (may be NULL) = the previous value. */

@@ -846,6 +846,12 @@ unsafe extern "C" {
     // points per interpreter launch
     pub fn r0hip_circuit_register(t: *const R0HipCircuitTables, t_size: usize) -> *const c_char;
     pub fn r0hip_testing_set_interp_chunk(points: u32, was: *mut u32) -> *const c_char;
+    // host-only: a circuit module (the circuit's generated kernels as a shared object of their
+    // own, include/r0hip_module.h) loaded at run time; loading runs its code, as linking it would.
+    // name_out (may be null) takes the circuit's name, name_cap >= 32. kind: 0 compiled in,
+    // 1 registered (interpreted), 2 a module.
+    pub fn r0hip_circuit_load(path: *const c_char, name_out: *mut c_char, name_cap: usize) -> *const c_char;
+    pub fn r0hip_circuit_backend(circuit: *const c_char, kind: *mut c_int) -> *const c_char;
     pub fn r0hip_prove_segment_cb(
         circuit: *const c_char,
         suite: c_int,

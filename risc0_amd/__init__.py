@@ -18,7 +18,8 @@ from .hal import (POSEIDON2, POSEIDON254, SHA256, BigIntBack, Buffer, HipHal, R0
                   VERIFY_RECEIPTS_DEVICE, ConstraintReport,
                   constraint_rows, constraint_term, set_witness_check, circuit_names, circuit_info,
                   prove_segment_cb, demo_witness, demo_accum, selftest, CircuitDesc, SelftestReport,
-                  CircuitTables, circuit_tables_struct, register_circuit, testing_set_interp_chunk)
+                  CircuitTables, circuit_tables_struct, register_circuit, testing_set_interp_chunk,
+                  load_circuit_module, circuit_backend, build_circuit_module, MODULE_DIR)
 
 __all__ = ["POSEIDON2", "POSEIDON254", "SHA256", "BigIntBack", "bigint_accum_inject", "bigint_accum_states", "bigint_accum_states_device", "bigint_backs", "BIGINT_BACK_DTYPE", "prove_recursion", "recursion_witgen", "rv32im_witgen", "prove_segment_trace", "ResidentTrace", "prove_segment_trace_resident", "Buffer", "HipHal", "R0HipError", "check", "exported_symbols", "last_profile",
            "lib", "mem_reset_peak", "mem_stats", "trim", "prove_segment", "prove_segment_accum", "prove_segments",
@@ -31,4 +32,5 @@ __all__ = ["POSEIDON2", "POSEIDON254", "SHA256", "BigIntBack", "bigint_accum_inj
            "VERIFY_RECEIPTS_DEVICE",
            "ConstraintReport", "constraint_rows", "constraint_term", "set_witness_check", "circuit_names", "circuit_info",
            "prove_segment_cb", "demo_witness", "demo_accum", "selftest", "CircuitDesc", "SelftestReport",
-           "CircuitTables", "circuit_tables_struct", "register_circuit", "testing_set_interp_chunk"]
+           "CircuitTables", "circuit_tables_struct", "register_circuit", "testing_set_interp_chunk",
+           "load_circuit_module", "circuit_backend", "build_circuit_module", "MODULE_DIR"]

@@ -44,7 +44,10 @@ struct CircuitDef {
   size_t n_ir;
   // A circuit registered at run time (r0hip_circuit_register, circuit_registry.cpp): the four
   // kernel pointers above are null and the device interprets these programs (eval_interp.hip).
-  // Null for every compiled-in circuit.
+  // Null for every compiled-in circuit, and null for a circuit loaded from a circuit module
+  // (r0hip_circuit_load): that one is a run-time entry too, but its four kernel pointers are the
+  // module's generated kernels and every table above points into the module, which stays open.
+  // So `interp` alone decides between the interpreter and the generated kernels.
   const rt::Programs* interp = nullptr;
 
   struct Tap {
@@ -73,16 +76,21 @@ const CircuitDef* compiled_find_circuit(const std::string& name);
 size_t compiled_circuit_count();
 const CircuitDef& compiled_circuit_at(size_t i);
 
-// Every circuit the process knows (circuit_registry.cpp): the compiled-in ones, then those
-// registered at run time in registration order. Readers take no lock: the registry is an
+// Every circuit the process knows (circuit_registry.cpp): the compiled-in ones, then the
+// run-time entries in the order they arrived, whether registered from tables
+// (r0hip_circuit_register, interpreted) or loaded from a circuit module (r0hip_circuit_load, its
+// own generated kernels); both kinds share the kMaxRegistered entries. Readers take no lock: the registry is an
 // append-only table of kMaxRegistered entries behind an atomic count, and an entry never moves
 // or goes away.
 constexpr size_t kMaxRegistered = 64;
 const CircuitDef* find_circuit(const std::string& name);
 size_t circuit_count();
 const CircuitDef& circuit_at(size_t i);
-// "unknown circuit X (compiled in: a, b, c)", and once anything is registered
-// "unknown circuit X (compiled in: a, b, c; registered: d)"
+// "unknown circuit X (compiled in: a, b, c)", and once there is a run-time entry
+// "unknown circuit X (compiled in: a, b, c; registered: d)": loaded names stand among the
+// registered ones under the same word
 std::string unknown_circuit(const char* name);
+// r0hip_circuit_backend: 0 compiled in, 1 registered (interpreted), 2 a module, -1 unknown
+int circuit_backend(const std::string& name);
 
 }  // namespace r0

@@ -144,6 +144,8 @@ def _declare(L):
         "r0hip_rv32im_bigint_accum_inject": [vp, sz, u32p, vp, sz],
         "r0hip_circuit_info": [C.c_char_p, vp, sz, C.c_char_p, sz],
         "r0hip_circuit_register": [vp, sz],
+        "r0hip_circuit_load": [C.c_char_p, C.c_char_p, sz],
+        "r0hip_circuit_backend": [C.c_char_p, C.POINTER(C.c_int)],
         "r0hip_testing_set_interp_chunk": [C.c_uint32, u32p],
         "r0hip_prove_segment_cb": [C.c_char_p, C.c_int, C.c_uint32, vp, vp, vp, vp, vp, C.c_int, C.c_uint32, u32p, sz,
                                    C.POINTER(sz), u32p],
@@ -546,6 +548,39 @@ def register_circuit(name, directory, files=None):
     t = circuit_tables.load(base + ".taps.json", base + ".poly.ir")
     s, keep = circuit_tables_struct(t, name)
     check(lib().r0hip_circuit_register(C.byref(s), C.sizeof(s)))
+
+
+def load_circuit_module(path):
+    """r0hip_circuit_load: load the circuit module at `path` (build_circuit_module) into this
+    process and return its circuit's name. Every circuit-generic call then takes the name and runs
+    the module's generated kernels, as a compiled-in circuit's. The library checks the module's
+    ABI number, struct sizes, architecture, tables and kernel view first and raises with the path
+    and what disagrees. Loading runs the module's code, exactly as linking it would. Host-only."""
+    name = C.create_string_buffer(64)
+    check(lib().r0hip_circuit_load(os.fsencode(path), name, 64))
+    return name.value.decode()
+
+
+def circuit_backend(name):
+    """r0hip_circuit_backend: 0 compiled in, 1 registered (interpreted on the device), 2 a circuit
+    module. Host-only."""
+    kind = C.c_int(-1)
+    check(lib().r0hip_circuit_backend(name.encode(), C.byref(kind)))
+    return int(kind.value)
+
+
+MODULE_DIR = os.path.join(_HERE, "modules")  # where the default build puts the tests' modules
+
+
+def build_circuit_module(name, directory, out, jobs=None):
+    """Compile the circuit of <directory>/<name>.poly.ir and <name>.taps.json (and
+    <name>.ectune.json, if there is one) into the circuit module `out` (`make module` in
+    risc0_amd/csrc: the generators, then hipcc for the library's architecture). Returns out."""
+    import subprocess
+    jobs = jobs or min(16, os.cpu_count() or 8)
+    subprocess.check_call(["make", "-C", os.path.join(_HERE, "csrc"), "-j", str(jobs), "module", f"NAME={name}",
+                           f"DIR={os.path.abspath(directory)}", f"OUT={os.path.abspath(out)}"])
+    return out
 
 
 def testing_set_interp_chunk(points):
