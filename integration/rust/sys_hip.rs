@@ -320,6 +320,10 @@ unsafe extern "C" {
     // its call counters {calls, drained, queued}
     pub fn r0hip_set_deferred(on: c_int, was: *mut c_int) -> *const c_char;
     pub fn r0hip_call_stats(out: *mut u64) -> *const c_char;
+    // {launched, in the program}: the kernels of this thread's last eval_check after its zero scan
+    pub fn r0hip_eval_check_launched(out: *mut c_int) -> *const c_char;
+    // the zero scan on its own: bit c of *h_mask = column c of the column-major matrix is all zero
+    pub fn r0hip_testing_zero_scan(d_matrix: *const u32, cols: usize, words: usize, h_mask: *mut u64) -> *const c_char;
     // streams one proof of the calling thread may use (1..3; for a worker proving one task at a time)
     pub fn r0hip_set_proof_streams(n: u32, was: *mut u32) -> *const c_char;
     // the calling thread's witness check: the provers evaluate the constraint polynomial on the

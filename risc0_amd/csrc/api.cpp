@@ -187,6 +187,22 @@ const char* r0hip_testing_set_interp_chunk(uint32_t points, uint32_t* was) {
     if (was) *was = w;
   });
 }
+const char* r0hip_testing_zero_scan(const uint32_t* d_matrix, size_t cols, size_t words, uint64_t* h_mask) {
+  return wrap([&] {
+    R0_REQUIRE(d_matrix && h_mask, "r0hip_testing_zero_scan: null argument");
+    R0_REQUIRE(cols <= size_t(kMaxGates), "r0hip_testing_zero_scan: more than 64 columns");
+    stage_reset();
+    std::vector<const uint32_t*> ptrs(cols);
+    for (size_t c = 0; c < cols; c++) ptrs[c] = d_matrix + c * words;
+    *h_mask = zero_scan_mask(ptrs, words);
+  });
+}
+const char* r0hip_eval_check_launched(int* out) {
+  return wrap_nosync([&] {
+    R0_REQUIRE(out != nullptr, "r0hip_eval_check_launched: null output");
+    eval_check_launched(out);
+  });
+}
 const char* r0hip_call_stats(uint64_t* out) {
   return wrap_nosync([&] {
     R0_REQUIRE(out != nullptr, "r0hip_call_stats: null output");

@@ -82,6 +82,16 @@ std::string check_kernel_view(const r0hip_circuit_tables& t, const EvalCheckInfo
   if (info.n_uniform < 0 || info.n_uniform > kMaxUniform)
     return f + "n_uniform: " + num(info.n_uniform) + " is not 0 to " + num(kMaxUniform);
   if (info.n_uniform && !info.uniform) return f + "uniform: NULL with n_uniform " + num(info.n_uniform);
+  // the gates: each a column of a witness group (the zero scan reads `rows` words of it)
+  if (info.ngates < 0 || info.ngates > kMaxGates)
+    return f + "ngates: " + num(info.ngates) + " is not 0 to " + num(kMaxGates);
+  if (info.ngates && (!info.gate_col || !info.plan)) return f + "gate_col, plan: NULL with ngates " + num(info.ngates);
+  for (int g = 0; g < info.ngates; g++) {
+    const int i = info.gate_col[g];
+    if (i < 0 || i >= info.ncols) return f + "gate_col: gate " + num(g) + " names column " + num(i) + " of " + num(info.ncols);
+    if (t.eval_args[info.col_arg[i]] < 0)
+      return f + "gate_col: gate " + num(g) + " is a column of mix or global, not of a witness group";
+  }
   return "";
 }
 

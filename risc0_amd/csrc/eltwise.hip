@@ -6,6 +6,8 @@
 // evaluate_any/poly_divide, which are integer-VALU bound.
 #include "runtime.h"
 
+#include "evalcheck_types.h"
+
 #include <map>
 
 #include <algorithm>
@@ -560,7 +562,49 @@ __global__ void rows_report_kernel(const uint4* vals, uint64_t n, uint32_t* out)
   }
 }
 
+// The zero scan of eval_check's gate columns (zero_scan; ec_zero_scan.h restates it for the host):
+// blockIdx.y is the column, a pointer to `words` words. flags is 64 bits in two words, cleared by
+// the launcher; bit g is set once a nonzero word of column g has been seen, so a bit is never set
+// for a column that is zero, whatever the order of the blocks. A wave ORs what its lanes load,
+// ballots, and lane 0 sets the bit with one atomicOr. It stops at the first load that held a
+// nonzero word, and a wave that starts after the bit is set does not read at all: a column that is
+// dense costs a fraction of one pass, a zero column exactly one.
+__global__ void zero_scan_kernel(const uint32_t* const* cols, uint64_t words, uint32_t* flags) {
+  const uint32_t g = blockIdx.y;
+  uint32_t* flag = flags + (g >> 5);
+  const uint32_t bit = 1u << (g & 31u);
+  if (__atomic_load_n(flag, __ATOMIC_RELAXED) & bit) return;  // one address: the whole wave agrees
+  const uint32_t* p = cols[g];
+  const uint64_t first = uint64_t(blockIdx.x) * kThreads + threadIdx.x, stride = uint64_t(gridDim.x) * kThreads;
+  uint32_t v = 0;
+  if ((reinterpret_cast<uintptr_t>(p) & 15u) == 0 && (words & 3u) == 0) {
+    const uint4* q = reinterpret_cast<const uint4*>(p);
+    for (uint64_t i = first; i < words / 4; i += stride) {
+      const uint4 t = q[i];
+      v |= t.x | t.y | t.z | t.w;
+      if (__ballot(v != 0)) break;
+    }
+  } else {
+    for (uint64_t i = first; i < words; i += stride) {
+      v |= p[i];
+      if (__ballot(v != 0)) break;
+    }
+  }
+  if (__ballot(v != 0) && (threadIdx.x & 63u) == 0) atomicOr(flag, bit);
+}
+
 }  // namespace
+
+void zero_scan(hipStream_t s, const uint32_t* const* cols, int n, size_t words, uint32_t* flags) {
+  static_assert(kThreads % 64 == 0, "zero_scan_kernel ballots whole waves");
+  R0_REQUIRE(n >= 0 && n <= kMaxGates, "zero_scan: more than 64 columns");
+  HIP_OK(hipMemsetD32Async(flags, 0u, 2, s));
+  if (!n || !words) return;
+  const size_t blocks = (words + 4 * kThreads - 1) / (4 * kThreads);
+  hipLaunchKernelGGL(zero_scan_kernel, dim3(unsigned(blocks < 1024 ? blocks : 1024), unsigned(n)), dim3(kThreads), 0, s,
+                     cols, uint64_t(words), flags);
+  HIP_OK(hipGetLastError());
+}
 
 void eltwise_add(hipStream_t s, uint32_t* out, const uint32_t* a, const uint32_t* b, size_t n) {
   if (!n) return;

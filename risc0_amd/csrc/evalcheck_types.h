@@ -1,12 +1,16 @@
 // The two plain structs that travel between the host driver and a circuit's generated kernels
 // (evalcheck.h). No HIP header: a circuit module's descriptor (include/r0hip_module.h) states
 // their sizes, and the load path's host checks (circuit_module.cpp) read EvalCheckInfo in
-// programs that link no HIP. A change to either struct changes R0HIP_MODULE_ABI.
+// programs that link no HIP. A change to either struct changes R0HIP_MODULE_ABI, with the one
+// exception recorded in include/r0hip_module.h.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
 
 namespace r0 {
+
+// the most gates a generated program may name (EvalCheckInfo::ngates): the bits of EvalCheckArgs::dead
+constexpr int kMaxGates = 64;
 
 struct EvalCheckArgs {
   const uint32_t* const* args;  // poly_fp argument buffers, circuit order
@@ -23,6 +27,9 @@ struct EvalCheckArgs {
   uint32_t tile = 0;            // points per tile (0 = whole domain per launch)
   int64_t wide = -1;            // bit k: kernel k addresses taps from colptr (-1 = tuned default)
   const uint32_t* uniform = nullptr;  // info.uniform's table (4 words per value), on the device
+  // bit g: the column of gate g (info.gate_col) is zero in all `domain` points, so the kernels that
+  // info.plan leaves out for this mask are not launched (0 = every kernel, whatever the columns hold)
+  uint64_t dead = 0;
 };
 
 struct EvalCheckInfo {
@@ -40,6 +47,12 @@ struct EvalCheckInfo {
   // and the poly_mix powers (FpExt AoS)
   int n_uniform;
   void (*uniform)(const uint32_t* const* g, const uint32_t* poly_mix, uint32_t* out);
+  // gates: columns that enter terms of poly_fp as a plain factor, as indices into col_arg/col_idx
+  // (at most kMaxGates). A gate whose column is zero everywhere makes its terms contribute 0; plan(dead)
+  // is the set of kernels (bit k, of `kernels`) the launcher runs for the mask `dead` of such gates.
+  int ngates;
+  const int* gate_col;
+  uint64_t (*plan)(uint64_t dead);
 };
 
 }  // namespace r0

@@ -21,6 +21,7 @@
 #include "../../include/r0hip.h"
 #include "circuit.h"
 #include "devmem.h"
+#include "ec_zero_scan.h"
 #include "eval_interp.h"
 #include "plugin.h"
 #include "runtime.h"
@@ -352,6 +353,30 @@ void ec_tables(const CircuitDef& c, const EvalCheckInfo& info, const uint32_t* c
   e.domain = uint32_t(domain);
 }
 
+// The gates (EvalCheckInfo) whose columns are zero in all `domain` points of the buffers as they
+// were handed over: one zero_scan launch over the gate columns, then its 8 bytes back, which
+// drains the thread's stream. The whole domain is read, so the answer holds for any caller's
+// buffers, not only for low-degree extensions of a trace. R0_EC_SKIP=0 (read on every call)
+// turns the scan off: no gate is reported, and every kernel runs.
+thread_local int t_ec_launched[2] = {0, 0};
+
+uint64_t ec_dead_gates(const EvalCheckInfo& info, const std::vector<const uint32_t*>& args, size_t domain) {
+  const char* skip_env = getenv("R0_EC_SKIP");
+  if (info.ngates <= 0 || !info.plan || (skip_env && skip_env[0] == '0' && !skip_env[1])) return 0;
+  std::vector<const uint32_t*> cols(info.ngates);
+  for (int g = 0; g < info.ngates; g++) {
+    const int i = info.gate_col[g];
+    cols[g] = args[info.col_arg[i]] + size_t(info.col_idx[i]) * domain;
+  }
+  return zero_scan_mask(cols, domain);
+}
+
+// what the launcher will do with e.dead, for eval_check_launched
+void ec_count(const EvalCheckInfo& info, uint64_t dead) {
+  t_ec_launched[0] = info.plan ? __builtin_popcountll(info.plan(dead)) : info.kernels;
+  t_ec_launched[1] = info.kernels;
+}
+
 // A circuit registered at run time has no generated kernels: its constraint program is
 // interpreted (eval_interp.hip) over n points, the eval_check form into `check` or the rows form
 // into `acc`. The poly_mix table is map_pow(poly_mix, poly_mix_powers) and nothing else. The
@@ -382,6 +407,20 @@ InterpRun run_interp(const CircuitDef& c, bool rows, const uint32_t* const* grou
 }
 }  // namespace
 
+uint64_t zero_scan_mask(const std::vector<const uint32_t*>& cols, size_t words) {
+  const int n = int(cols.size());
+  auto* flags = static_cast<uint32_t*>(scratch(8, kSlotEcGateFlags));
+  zero_scan(stream(), reinterpret_cast<const uint32_t* const*>(upload(cols, kSlotEcGatePtr)), n, words, flags);
+  uint32_t seen[2];
+  d2h(seen, flags, sizeof seen);
+  return zero_scan_dead(uint64_t(seen[0]) | (uint64_t(seen[1]) << 32), n);
+}
+
+void eval_check_launched(int out[2]) noexcept {
+  out[0] = t_ec_launched[0];
+  out[1] = t_ec_launched[1];
+}
+
 // eval_check for one circuit (rv32im/src/prove/hal/cpu.rs:145-207 semantics)
 void run_eval_check(const CircuitDef& c, uint32_t* check, const uint32_t* const* groups, const uint32_t* mix,
                     const uint32_t* global, FpExt poly_mix, size_t po2, const uint32_t* h_mix,
@@ -402,6 +441,7 @@ void run_eval_check(const CircuitDef& c, uint32_t* check, const uint32_t* const*
     Span span("eval_check");
     KScope ks("eval_check_interp", bytes, double(domain) * (c.interp->modmuls + 4));
     run_interp(c, false, groups, mix, global, poly_mix, domain, upload(vinv, kSlotEcVinv), check, nullptr);
+    t_ec_launched[0] = t_ec_launched[1] = 0;
     return;
   }
   EvalCheckInfo info;
@@ -428,6 +468,8 @@ void run_eval_check(const CircuitDef& c, uint32_t* check, const uint32_t* const*
   for (int g = 0; g < 3; g++) bytes += 4.0 * domain * c.group_sizes[g];
   Span span("eval_check");
   KScope ks("eval_check", bytes, double(domain) * info.modmuls_per_point);
+  e.dead = ec_dead_gates(info, args, domain);
+  ec_count(info, e.dead);
   c.eval_check(s, e);
 }
 
@@ -450,6 +492,7 @@ void constraint_rows_run(const CircuitDef& c, size_t po2, const uint32_t* const*
     Span span("constraint_rows");
     KScope ks("constraint_rows_interp", bytes, double(rows) * c.interp->modmuls);
     run_interp(c, true, groups, mix, global, poly_mix, rows, nullptr, nullptr, e.acc);
+    t_ec_launched[0] = t_ec_launched[1] = 0;
     rows_report(s, e.acc, rows, d_rep);
   } else {
     EvalCheckInfo info;
@@ -462,6 +505,8 @@ void constraint_rows_run(const CircuitDef& c, size_t po2, const uint32_t* const*
     for (int g = 0; g < 3; g++) bytes += 4.0 * rows * c.group_sizes[g];
     Span span("constraint_rows");
     KScope ks("constraint_rows", bytes, double(rows) * info.modmuls_per_point);
+    e.dead = ec_dead_gates(info, args, rows);
+    ec_count(info, e.dead);
     c.constraint_rows(s, e);
     rows_report(s, e.acc, rows, d_rep);
   }

@@ -74,6 +74,8 @@ enum ScratchSlot : int {
   kSlotEcPolyMixNb = 25,
   kSlotEcColPtr = 26,
   kSlotEcInterp = 28,   // the interpreter's slot file (eval_interp.hip), a run-time circuit's only
+  kSlotEcGatePtr = 29,  // the zero scan's column pointers and its two flag words
+  kSlotEcGateFlags = 30,
   kSlotEcUniform = 27,  // prover uploads (prover.cpp): evaluation points per group (3 groups), check points,
   // mix_poly_coeffs row lists, combos deltas, query gather tables
   kSlotTapXs = 33,  // .. 35
@@ -358,6 +360,16 @@ bool set_witness_check_mode(bool on) noexcept;  // returns the previous mode
 // out[2] = the smallest nonzero index, out[3..19) = the 16 smallest in ascending order
 // (0xFFFFFFFF where there is none); 19 words.
 void rows_report(hipStream_t s, const uint32_t* vals, size_t n, uint32_t* out);
+// zero_scan (eltwise.hip): cols is a device table of n <= 64 pointers to `words` words each;
+// flags (two device words, cleared here first) gets bit g set when column g holds a nonzero word.
+void zero_scan(hipStream_t s, const uint32_t* const* cols, int n, size_t words, uint32_t* flags);
+// The scan over device columns given on the host, its flags read back (prover.cpp): bit g of the
+// result = column g is zero in all `words` words. Drains the thread's stream.
+uint64_t zero_scan_mask(const std::vector<const uint32_t*>& cols, size_t words);
+// The kernels the calling thread's last eval_check launched and the kernels its program has (the
+// zero scan's effect, prover.cpp; r0hip_eval_check_launched). 0, 0 before the first call and after
+// an interpreted one.
+void eval_check_launched(int out[2]) noexcept;
 
 // Element-wise and polynomial kernels (eltwise.hip).
 void eltwise_add(hipStream_t s, uint32_t* out, const uint32_t* a, const uint32_t* b, size_t n);

@@ -78,6 +78,8 @@ def _declare(L):
         "r0hip_set_deferred": [C.c_int, C.POINTER(C.c_int)],
         "r0hip_set_proof_streams": [C.c_uint32, C.POINTER(C.c_uint32)],
         "r0hip_call_stats": [C.POINTER(C.c_uint64)],
+        "r0hip_eval_check_launched": [C.POINTER(C.c_int)],
+        "r0hip_testing_zero_scan": [vp, sz, sz, C.POINTER(C.c_uint64)],
         "r0hip_batch_expand_into_evaluate_ntt": [vp, vp, sz, C.c_uint32, C.c_uint32],
         "r0hip_batch_interpolate_ntt": [vp, sz, C.c_uint32],
         "r0hip_zk_shift": [vp, sz, C.c_uint32],
@@ -1746,6 +1748,24 @@ def kernel_times():
             ms, calls, b, mm = v.split(":")
             out[k] = (float(ms), int(calls), float(b), float(mm))
     return out
+
+
+def eval_check_launched():
+    """(launched, kernels) of the calling thread's last eval_check or constraint-rows check
+    (r0hip_eval_check_launched): how many of the program's kernels ran after the zero scan of the
+    selector columns."""
+    out = (C.c_int * 2)()
+    check(lib().r0hip_eval_check_launched(out))
+    return int(out[0]), int(out[1])
+
+
+def zero_scan(matrix, cols, words):
+    """r0hip_testing_zero_scan: the mask of the all-zero columns (bit c) among `cols` columns of `words`
+    words, laid one after the other from `matrix` (a Buffer or a device address)."""
+    mask = C.c_uint64(0)
+    check(lib().r0hip_testing_zero_scan(C.c_void_p(matrix.ptr if isinstance(matrix, Buffer) else matrix), cols, words,
+                                C.byref(mask)))
+    return int(mask.value)
 
 
 def call_stats():

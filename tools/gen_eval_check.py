@@ -27,8 +27,12 @@ that depend only on constants, mix and global words are evaluated once on the ho
 REDC per sum ("fuse"), and tap addressing by column base pointers ("wide").
 
 Usage: gen_eval_check.py CIRCUIT OUTDIR [BUDGET]
-Writes OUTDIR/eval_check_<circuit>_k<i>.hip (one per kernel, compiled in parallel)
-and OUTDIR/eval_check_<circuit>.hip (launcher).
+Writes OUTDIR/eval_check_<circuit>_k<i>.hip (one per kernel, compiled in parallel),
+OUTDIR/eval_check_<circuit>.hip (launcher) and OUTDIR/eval_check_<circuit>_fin.hip (the finishing
+kernel). The launcher carries the gates and plan() (gate_tables, plan_fn): a kernel all of whose
+terms are gated by a selector column that is zero on the whole domain is not launched
+(EvalCheckArgs::dead), and the finishing kernel stands in for a last kernel left out that way.
+The kernels' own text does not depend on any of this.
 
 A second family from the same program, OUTDIR/rows_<circuit>_k<i>.hip and OUTDIR/rows_<circuit>.hip
 (constraint_rows_<circuit>, emit(rows=True)): poly_fp on the N trace rows themselves, taps at
@@ -569,6 +573,76 @@ def uniform_fn(pg):
     return L
 
 
+MAX_GATES = 64  # kMaxGates (evalcheck_types.h); the launcher and the host unit assert it
+
+
+def gate_tables(pg, kernels):
+    """Gates: the distinct (argument, column) whose tap load is a ("v", U) factor of some term
+    expr * prod(U) * pm, at any `back`. A gate column that is zero on the whole domain makes every
+    term it gates contribute exactly 0. Returns (gates, kernel_gates): the gates in order of first
+    appearance (at most MAX_GATES; a further one is treated as never zero), and per kernel the
+    gate lists of its terms, or None for a kernel that always runs: kernel 0 (it defines the
+    accumulator), a kernel that stores a materialised value, a kernel with no term."""
+    gates = {}
+    kernel_gates = []
+    for ki, items in enumerate(kernels):
+        items = [it for it in items if it[2] != "mat" or it[3] in pg.mat]
+        lists = []
+        for it in items:
+            if it[2] != "term":
+                continue
+            gl = []
+            for x in it[3][1]:
+                ins = pg.byid[x[1]] if x[0] == "v" else None
+                if ins is None or ins[0] != "l":
+                    continue
+                key = (ins[2], ins[3])
+                if key not in gates and len(gates) < MAX_GATES:
+                    gates[key] = len(gates)
+                if key in gates and gates[key] not in gl:
+                    gl.append(gates[key])
+            lists.append(sorted(gl))
+        always = ki == 0 or not lists or any(it[2] == "mat" for it in items)
+        kernel_gates.append(None if always else lists)
+    return sorted(gates, key=gates.get), kernel_gates
+
+
+def plan_fn(gates, kernel_gates, colslot, finish):
+    """The launch decision as plain C++, compiled by the device launcher and by the --host
+    translation unit alike: plan(dead) is the set of kernels to launch (bit k: kernel k) when the
+    columns of the gates in `dead` (bit g: gate g) are zero everywhere. A kernel is left out when
+    it may be (gate_tables) and every one of its terms has a dead gate; a term without a gate is
+    always live, so plan(0) is every kernel."""
+    nk = len(kernel_gates)
+    L = ["// Gates: trace columns that enter terms of poly_fp as a plain factor (selectors). A gate whose",
+         "// column is zero on the whole domain makes each term it gates contribute exactly 0, so a",
+         "// kernel that holds only such terms (and stores no materialised value) need not run.",
+         f"constexpr int NGATE = {len(gates)};",
+         "static_assert(NGATE <= kMaxGates, \"one bit of EvalCheckArgs::dead per gate\");",
+         "// a finishing kernel takes the place of a last kernel that is left out",
+         f"constexpr bool kFinish = {'true' if finish else 'false'};",
+         "// slot of each gate's column in kColArg/kColIdx",
+         f"const int kGateCol[] = {{{', '.join(str(colslot[g]) for g in gates) or '0'}}};"]
+    for k, lists in enumerate(kernel_gates):
+        if lists is None:
+            L.append(f"// k{k}: always runs")
+        else:
+            L.append(f"// k{k}: {len(lists)} terms, gates " + " ".join(
+                "[" + ",".join(f"{gates[g][0]}:{gates[g][1]}" for g in gl) + "]" for gl in lists))
+    L += ["// the kernels to launch (bit k) when the gates in `dead` (bit g) are zero everywhere",
+          "uint64_t plan(uint64_t dead) {",
+          f"  uint64_t run = {(1 << nk) - 1}ull;",
+          "  (void)dead;"]
+    for k, lists in enumerate(kernel_gates):
+        if lists is None or any(not gl for gl in lists):
+            continue
+        masks = sorted(set(sum(1 << g for g in gl) for gl in lists))
+        cond = " && ".join(f"(dead & {m}ull)" for m in masks)
+        L.append(f"  if ({cond}) run &= ~(1ull << {k});")
+    L += ["  return run;", "}"]
+    return L
+
+
 def emit(circuit, outdir, budget, host=False, rows=False):
     """rows=False: the eval_check family (the 4N evaluation domain, tuned by <circuit>.ectune.json).
     rows=True: the constraint-rows family (rows_<circuit>*.hip, namespace rows_<circuit>): the same
@@ -612,6 +686,7 @@ def emit(circuit, outdir, budget, host=False, rows=False):
             split_kernels.append(piece)
     kernels = split_kernels
     prog, types = pg.prog, pg.types
+    gates, kernel_gates = gate_tables(pg, kernels)
     nargs = 1 + max(ins[2] for ins in prog if ins[0] in ("l", "g"))
     npm = max([ins[4] for ins in prog if ins[0] == "a"] + [ins[5] for ins in prog if ins[0] == "b"]) + 1
     mat = sorted(pg.mat, key=lambda v: pg.order[v])
@@ -1475,16 +1550,25 @@ def emit(circuit, outdir, budget, host=False, rows=False):
         f"  info->modmuls_per_point = {modmuls(pg) + (0 if rows else 4)};",
         f"  info->ncols = {len(colslot)}; info->col_arg = {ns}::kColArg; info->col_idx = {ns}::kColIdx;",
         f"  info->n_uniform = {ns}::NUV; info->uniform = {ns}::uniform;",
+        f"  info->ngates = {ns}::NGATE; info->gate_col = {ns}::kGateCol; info->plan = {ns}::plan;",
         "}",
     ]
     combos_line = f"const int kPmCombos[] = {{{', '.join(str(x) for x in flat) or '0'}}};"
     cols = sorted(colslot, key=colslot.get)
     combos_line += (f"\nconst int kColArg[] = {{{', '.join(str(a) for a, _ in cols)}}};"
                     f"\nconst int kColIdx[] = {{{', '.join(str(c) for _, c in cols)}}};")
+    # what the last kernel does besides its own terms. The accumulator holds canonical words, so
+    # this is the last kernel's result when all its terms are 0. The rows family's last kernel
+    # leaves the sum in A.acc, where it already is: nothing takes a dead last kernel's place.
+    fin_body = [] if rows else [
+        "  const uint4 p = reinterpret_cast<const uint4*>(A.acc)[cycle];",
+        "  const FpExt s = fe_mul_fp(FpExt{{p.x, p.y, p.z, p.w}}, A.vinv[cycle & 3]);",
+        "  for (int k = 0; k < 4; k++) A.check[uint64_t(k) * A.domain + cycle] = s.c[k];",
+    ]
     if host:
         # one host translation unit: every kernel body as a per-point function, for the
         # CPU check of the generated arithmetic (tests/test_ec_host.py)
-        T = ["#define R0_EC_HOST 1", "#include <stddef.h>", "#include <stdint.h>",
+        T = ["#define R0_EC_HOST 1", "#include <stddef.h>", "#include <stdint.h>", '#include "evalcheck_types.h"',
              "struct uint4 { uint32_t x, y, z, w; };",
              "static inline uint4 make_uint4(uint32_t x, uint32_t y, uint32_t z, uint32_t w) { return uint4{x, y, z, w}; }",
              head]
@@ -1494,18 +1578,47 @@ def emit(circuit, outdir, budget, host=False, rows=False):
             T.append("  const uint32_t mask = A.domain - 1;")
             T += L
             T.append("}")
+        T.append("static void kfin(const Args& A, uint32_t cycle) {")
+        T += fin_body
+        T.append("}")
         T.append(f"constexpr int NK = {len(bodies)};")
         T.append(f"static void (*const kTable[NK])(const Args&, uint32_t) = {{{', '.join(f'k{i}' for i in range(len(bodies)))}}};")
         T.append(combos_line)
         T += uniform_fn(pg)
+        T += plan_fn(gates, kernel_gates, colslot, not rows)
         T.append(f"}}  // namespace {ns}")
         T.append("}  // namespace r0")
         T += [
+            '#include "ec_zero_scan.h"',
             f'extern "C" int {hostfn}_combos(const int** combos, int* npm) {{',
             f"  *combos = r0::{ns}::kPmCombos; *npm = r0::{ns}::NPM; return {len(combo_index)};",
             "}",
+            "// the gates as (argument, column) pairs; returns how many, *kernels the program's kernel count",
+            f'extern "C" int {hostfn}_gates(int* arg, int* col, int* kernels) {{',
+            f"  using namespace r0::{ns};",
+            "  for (int g = 0; g < NGATE; g++) { arg[g] = kColArg[kGateCol[g]]; col[g] = kColIdx[kGateCol[g]]; }",
+            "  *kernels = NK;",
+            "  return NGATE;",
+            "}",
+            "// the zero scan's host restatement over the gate columns: bit g set = gate g is zero everywhere",
+            f'extern "C" uint64_t {hostfn}_scan(const uint32_t* const* args, uint32_t domain) {{',
+            f"  using namespace r0::{ns};",
+            "  const uint32_t* cols[NGATE ? NGATE : 1];",
+            "  for (int g = 0; g < NGATE; g++) cols[g] = args[kColArg[kGateCol[g]]] + size_t(kColIdx[kGateCol[g]]) * domain;",
+            "  return r0::zero_scan_host(cols, NGATE, domain);",
+            "}",
+            f'extern "C" int {hostfn}_skip(const uint32_t* const* args, const uint32_t* pm, const uint32_t* pmn,',
+            "    const uint32_t* vinv, uint32_t* acc, uint32_t* mf, uint32_t* me, uint32_t* check, uint32_t domain,",
+            "    uint64_t dead);",
             f'extern "C" void {hostfn}(const uint32_t* const* args, const uint32_t* pm, const uint32_t* pmn,',
             "    const uint32_t* vinv, uint32_t* acc, uint32_t* mf, uint32_t* me, uint32_t* check, uint32_t domain) {",
+            f"  {hostfn}_skip(args, pm, pmn, vinv, acc, mf, me, check, domain, 0);",
+            "}",
+            "// the launcher's decision for `dead` (plan), as the device launcher takes it; returns how many of",
+            "// the program's kernels ran",
+            f'extern "C" int {hostfn}_skip(const uint32_t* const* args, const uint32_t* pm, const uint32_t* pmn,',
+            "    const uint32_t* vinv, uint32_t* acc, uint32_t* mf, uint32_t* me, uint32_t* check, uint32_t domain,",
+            "    uint64_t dead) {",
             f"  using namespace r0::{ns};",
             "  Args A;",
             f"  for (int i = 0; i < {nargs}; i++) A.a[i] = args[i];",
@@ -1517,11 +1630,37 @@ def emit(circuit, outdir, budget, host=False, rows=False):
             "  uint32_t uvt[4 * (NUV ? NUV : 1)];",
             "  uniform(args, pm, uvt);",
             "  A.uv = uvt;",
-            "  for (int k = 0; k < NK; k++)",
+            "  const uint64_t run = plan(dead);",
+            "  int launched = 0;",
+            "  for (int k = 0; k < NK; k++) {",
+            "    if (!((run >> k) & 1)) continue;",
+            "    launched++;",
             "    for (uint32_t c = 0; c < domain; c++) kTable[k](A, c);",
+            "  }",
+            "  if (kFinish && !((run >> (NK - 1)) & 1))",
+            "    for (uint32_t c = 0; c < domain; c++) kfin(A, c);",
+            "  return launched;",
             "}",
         ]
         return "\n".join(T) + "\n"
+
+    if not rows:
+        K = [head,
+             "// In place of a last kernel whose terms are all dead (plan): the accumulator as it stands,",
+             "// scaled by the vanishing polynomial's inverse, to the four check planes.",
+             "__global__ __launch_bounds__(256) void kfin(Args A) {",
+             "  const uint32_t cycle = A.base + blockIdx.x * 256u + threadIdx.x;",
+             "  if (cycle >= A.base + A.count) return;"]
+        K += fin_body
+        K += ["}",
+              "void launch_fin(hipStream_t s, const Args& A) {",
+              "  hipLaunchKernelGGL(kfin, dim3(div_up(A.count, 256)), dim3(256), 0, s, A);",
+              "  HIP_OK(hipGetLastError());",
+              "}",
+              f"}}  // namespace {ns}",
+              "}  // namespace r0"]
+        with open(os.path.join(outdir, f"{stem}_fin.hip"), "w") as f:
+            f.write("\n".join(K) + "\n")
 
     for ki, (L, kwaves) in enumerate(bodies):
         K = [head]
@@ -1551,8 +1690,13 @@ def emit(circuit, outdir, budget, host=False, rows=False):
     w = L.append
     for ki in range(len(kernels)):
         w(f"void launch_k{ki}(hipStream_t s, const Args& A);")
+    if not rows:
+        w("void launch_fin(hipStream_t s, const Args& A);")
+    w(f"constexpr int NK = {len(kernels)};")
+    w(f"static void (*const kLaunch[NK])(hipStream_t, const Args&) = {{{', '.join(f'launch_k{i}' for i in range(len(kernels)))}}};")
     w(combos_line)
     L += uniform_fn(pg)
+    L += plan_fn(gates, kernel_gates, colslot, not rows)
     w(f"}}  // namespace {ns}")
     L += info
     w(f"void {entry}(hipStream_t s, const EvalCheckArgs& e) {{")
@@ -1568,11 +1712,14 @@ def emit(circuit, outdir, budget, host=False, rows=False):
     w("  // tiles of e.tile points run every kernel before the next tile, so a tile's")
     w("  // trace columns are re-read from the Infinity Cache rather than HBM")
     w("  const uint32_t tile = e.tile ? e.tile : e.domain;")
+    w("  const uint64_t run = plan(e.dead);  // once per call: e.dead = 0 launches every kernel")
     w("  for (uint32_t b = 0; b < e.domain; b += tile) {")
     w("    A.base = b;")
     w("    A.count = e.domain - b < tile ? e.domain - b : tile;")
-    for ki in range(len(kernels)):
-        w(f"    launch_k{ki}(s, A);")
+    w("    for (int k = 0; k < NK; k++)")
+    w("      if ((run >> k) & 1) kLaunch[k](s, A);")
+    if not rows:
+        w("    if (!((run >> (NK - 1)) & 1)) launch_fin(s, A);")
     w("  }")
     w("}")
     w("}  // namespace r0")
